@@ -72,7 +72,12 @@ def parse():
     ap.add_argument("--plumbing", action="store_true",
                     help="CPU-only check of the N-rank path (gloo, fabricated burst records, no kernel)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py starts the ranks itself")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the events the headline mode's last timed step delivered (rank 0's channels) "
+                         "as DIR/<name>.npy, float64 / float32, at most 64 MB: two builds on the same arguments compare output for output")
     a = ap.parse_args()
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
     if a.channels is None:
         a.channels = 4096 if a.workload == "configs1" else 32768
     if a.seconds is None:
@@ -188,12 +193,14 @@ PREHEAT_MS = [350.0]      # --preheat-ms
 AGREE = [lambda v: v]     # N ranks: the maximum of v over the ranks (main() sets it)
 
 
-def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, want_steady=False):
+def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, want_steady=False, keep_last=False):
     """W untimed + K timed passes.  Each pass launches one batch; the library collects the
     previous batch's event log (copy back, ordering, transport layer) while the new launch
     runs, so a pass consumes the events of the batch before it and the last batch is
     drained after the loop -- inside the timed region.  Returns (elapsed_s, mean kernel ms,
-    events of the first pass, bursts gathered from the last drained batch)."""
+    events of the first pass, bursts gathered from the last drained batch).  keep_last: the
+    events of the last timed launch, sample counters from the start of its call, are left in
+    run_steps.last_events (copied after the timed region; None without it or with K = 0)."""
     import numpy as np
     import torch
     kernel_ms = []
@@ -201,6 +208,7 @@ def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, wa
     first = []
     keep_first = [True]
     last_bursts = [0]
+    keep = [False]           # (keep_last) the final drain leaves the queue as it is: the events are copied after the timed region
 
     def consume():
         # non-blocking: what the host already has.  The queue holds compact records; a consumer that only gathers the
@@ -215,7 +223,8 @@ def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, wa
                 first.append(rx.peek_events_np().copy())
                 keep_first[0] = False
             last_bursts[0] = gather(rx)    # (copies the burst records out of the queue)
-            rx.drop_events(n_ev)
+            if not keep[0]:
+                rx.drop_events(n_ev)
 
     n_launches = [0]
 
@@ -269,15 +278,27 @@ def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, wa
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     marks = []
-    for _ in range(steps):
+    t_last = 0
+    for i in range(steps):
+        if keep_last and i == steps - 1:
+            t_last = rx.input_sample_counter()
         one_pass()
         marks.append(time.perf_counter())
+    keep[0] = keep_last and steps > 0
     drain()
+    keep[0] = False
     marks.append(time.perf_counter())
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    run_steps.last_events = None
+    if keep_last and steps > 0:
+        ev = rx.peek_events_np()
+        last = ev[ev["sample_counter"] > t_last].copy()
+        last["sample_counter"] -= t_last
+        rx.drop_events(len(ev))
+        run_steps.last_events = last
     if os.environ.get("SAME_BENCH_DEBUG"):
         sys.stderr.write("per-pass wall ms (last = drain): " + " ".join(f"{1e3 * (b - a):.2f}" for a, b in zip([t0] + marks[:-1], marks)) + "\n")
         sys.stderr.write("kernel ms per launch: " + " ".join(f"{k:.3f}" for k in kernel_ms) + " | demod alone: " + " ".join(f"{k:.3f}" for k in demod_ms) + "\n")
@@ -299,6 +320,53 @@ def run_steps(sa, rx, x, T, stream, steps, warmup, gather, barrier, layout=0, wa
         rx.drop_events(len(ev))
     run_steps.last_launches = n_launches[0]      # (warm-up, pre-heat, timed and the steady pass: tools/profile_collect.py sorts a trace's launches by block with it)
     return elapsed, k_mean, first_ev, last_bursts[0], steady
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_CHANNELS = 4096
+
+
+def dump_outputs(d, ev, n_channels, seed=0):
+    """--dump-outputs: the events one step handed its caller (EVENT_DTYPE, sample counters from the start of the step's call), one
+    array per field.  Events are ordered by (channel, sample counter), the library's order among equals.  symbol_offset is the
+    squelch symbol count from the channel's first event of the step (the absolute count depends on how many untimed passes ran
+    before); payload is every event's first `len` bytes, concatenated.  Above DUMP_MAX_CHANNELS channels, or DUMP_MAX_BYTES in
+    all, a seeded sample of channels (channels.npy: which ones) -- the first of the same permutation whatever its size."""
+    import numpy as np
+    if n_channels <= DUMP_MAX_CHANNELS:
+        perm = np.arange(n_channels)
+    else:
+        perm = np.random.default_rng(seed).permutation(n_channels)
+    ev = ev[np.lexsort((ev["sample_counter"], ev["channel"]))]
+    n = min(n_channels, DUMP_MAX_CHANNELS)
+    while True:
+        chans = np.sort(perm[:n])
+        sel = ev[np.isin(ev["channel"], chans)]
+        size = 8 * (len(chans) + 7 * len(sel)) + 4 * int(sel["len"].astype(np.int64).sum())
+        if size <= DUMP_MAX_BYTES or n == 1:
+            break
+        n //= 2
+    sym0 = {}
+    for c, s in zip(sel["channel"].tolist(), sel["symbol_count"].tolist()):
+        sym0.setdefault(c, s)
+    first_sym = np.array([sym0[c] for c in sel["channel"].tolist()], dtype=np.uint64)
+    lens = sel["len"].astype(np.int64)
+    arrays = {
+        "channels": chans.astype(np.float64),
+        "event_channel": sel["channel"].astype(np.float64),
+        "event_kind": sel["kind"].astype(np.float64),
+        "event_sample_offset": sel["sample_counter"].astype(np.float64),
+        "event_symbol_offset": (sel["symbol_count"] - first_sym).astype(np.float64),
+        "event_len": lens.astype(np.float64),
+        "event_aux": sel["aux"].astype(np.float64),
+        "event_aux2": sel["aux2"].astype(np.float64),
+        "event_payload": (sel["bytes"][np.arange(sel["bytes"].shape[1])[None, :] < lens[:, None]].astype(np.float32)
+                          if len(sel) else np.zeros(0, dtype=np.float32)),
+    }
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return arrays
 
 
 def tp_contract(sa, ev_strict, ev_tp, C, seed, what="first pass", t_end=None, rate=22050):
@@ -513,9 +581,9 @@ def main():
                     os.environ[k] = v
         r.set_kernel_timing(True)
         el, kms, first_ev, nb, steady = run_steps(sa, r, x if xin is None else xin, T, stream, args.steps, args.warmup, gather, barrier,
-                                                  layout=layout, want_steady=True)
+                                                  layout=layout, want_steady=True, keep_last=bool(args.dump_outputs) and rank == 0)
         facts = {"kernel": r.kernel_name(), "chunks": int(r.time_parallel_chunks()), "per_channel": bool(r.time_parallel_per_channel()),
-                 "demod_ms": run_steps.last_demod_ms, "launches": run_steps.last_launches}
+                 "demod_ms": run_steps.last_demod_ms, "launches": run_steps.last_launches, "last_events": run_steps.last_events}
         del r
         return max_over_ranks(el), kms, first_ev, nb, steady, facts
 
@@ -637,6 +705,10 @@ def main():
         # with the host's jitter from run to run; `value` is then that mode's whole step)
         headline = max(ok, key=lambda m: modes[m]["roofline"]["achieved"]) if ok else "strict"
     hb = modes[headline]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runs[headline][5]["last_events"], C)
+    for r_ in runs.values():
+        r_[5].pop("last_events", None)
     out = {
         "metric": "Msamples/s demodulated (batched 22.05 kHz channels) + % HBM roofline, 1/8 GPU",
         "value": hb["value"],
