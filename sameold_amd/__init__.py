@@ -8,5 +8,5 @@ from .receiver import (  # noqa: F401
     LAYOUT_CHANNEL_MAJOR, LAYOUT_TIME_MAJOR,
     LINK_BURST, LINK_NO_CARRIER, LINK_READING, LINK_SEARCHING,
     TRANSPORT_ASSEMBLING, TRANSPORT_IDLE, TRANSPORT_MSG_END, TRANSPORT_MSG_ERR, TRANSPORT_MSG_START,
-    load_library, synth_afsk, synth_payload,
+    decode_recordings, load_library, synth_afsk, synth_payload,
 )

@@ -26,6 +26,7 @@
 #include "same_config.h"
 #include "same_device.h"
 #include "same_launch.h"
+#include "same_resets.h"
 #include "same_transport.h"
 
 namespace {
@@ -246,6 +247,9 @@ struct same_batch {
         uint32_t *d_geom = nullptr;      // [own_start | row0 | nominal | perm] x columns, then wg_blocks
         uint32_t *h_geom = nullptr;      // pinned: own_start | row0
         size_t geom_cap = 0;
+        // channels re-initialised in front of this launch (same_batch_reset_channels): pinned, mapped, read by the reset kernel
+        uint32_t *h_reset = nullptr, *h_reset_dev = nullptr;
+        uint32_t reset_cap = 0;
     } slot[2];
     // time-parallel mode (SAME_BATCH_TIME_PARALLEL)
     struct TimePar {
@@ -336,6 +340,9 @@ struct same_batch {
     std::vector<same::TransportCold> tcold;
     same::TransportRef tr(uint32_t c) { return same::TransportRef(thot[c], tcold[c]); }
     uint64_t *h_wake = nullptr;      // host mirror of State::wake_sample (pinned, n_channels words, zero = unarmed)
+    // per-channel resets (same_batch_reset_channels): where each half of a reset is due, the channels' counter bases
+    same::ResetLedger resets;
+    std::vector<uint32_t> reset_list, reset_now, reset_cols;       // scratch: the entry point's, the reset kernel's list
 };
 
 static void release_stale_view(same_batch *rx);
@@ -522,6 +529,44 @@ hipError_t launch_fm(const same::Params &Pv, const same::State &Sv, const same::
     }
 }
 
+// The host half of a reset of channel c at stream position `pos` (same_batch_reset_channels): the transport layer goes Idle and
+// forgets its bursts, pending message and forced-EOM instant (receiver.rs:195-196); the time-parallel symbol clock restarts at
+// `pos` (the device's symbol counter of the channel restarts there too); the channel's wake-up entry is cleared (the reset kernel
+// clears the device's copy)
+void reset_channel_host(same_batch *rx, uint32_t c, uint64_t pos)
+{
+    if (!rx->thot.empty()) rx->tr(c).reset();
+    if (rx->tp.enabled) {
+        rx->tp.sym_off[c] = 0;
+        rx->tp.synth[c].reset();
+        rx->tp.synth[c].a_t = pos;
+    }
+    if (rx->h_wake) rx->h_wake[c] = 0;
+}
+
+// The device half of the resets asked for since the last launch: the channels' state columns re-initialised on the stream of
+// the launch about to be queued, in front of it.  The list goes through this slot's pinned buffer, which the kernel reads in
+// place (no copy in the stream); the slot's previous launch -- and the reset kernel in front of it -- has been harvested.
+int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stream)
+{
+    if (rx->resets.device.empty()) return SAME_OK;
+    std::vector<uint32_t> &cols = rx->reset_cols;
+    rx->resets.take_device(cols);
+    const uint32_t n = (uint32_t)cols.size();
+    if (n > sl.reset_cap) {
+        if (sl.h_reset) HIP_TRY(hipHostFree(sl.h_reset));
+        sl.h_reset = nullptr; sl.h_reset_dev = nullptr; sl.reset_cap = 0;
+        const uint32_t want = std::max<uint32_t>(256u, n + n / 2u);
+        HIP_TRY(hipHostMalloc((void **)&sl.h_reset, (size_t)want * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_reset_dev, sl.h_reset, 0));
+        sl.reset_cap = want;
+    }
+    std::memcpy(sl.h_reset, cols.data(), (size_t)n * sizeof(uint32_t));
+    const hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset_dev, n, stream);
+    if (e != hipSuccess) return fail(SAME_EHIP, "channel reset launch failed: %s", hipGetErrorString(e));
+    return SAME_OK;
+}
+
 // The host half of a harvest: the launch's ordered event log, burst pool, hand-over instants and chunk geometry are in the
 // slot's host buffers; order each column's records, replay the channels (stitch + transport layer) on the worker threads and
 // append to the queue.  Touches no device: same_debug_harvest_replay runs it on a recorded launch without one.
@@ -589,9 +634,11 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     // one device event -> the link event of channel c (+ the transport event it causes).  `off`: what
     // the time-parallel mode adds to the device's symbol count (0 otherwise).
     // (transport events arrive as same_rx_event from the transport layer: kept as a record + payload)
+    // (the stitch and the transport layer work on the device's counters, from the batch's first sample; a queue record counts
+    // from its channel's last reset: same_batch_reset_channels)
     auto push_transport = [&](Part &part, const same_rx_event &tev, uint32_t c) {
         QEvent q{};
-        q.kind = tev.kind; q.channel = c; q.sample_counter = tev.sample_counter; q.symbol_count = tev.symbol_count;
+        q.kind = tev.kind; q.channel = c; q.sample_counter = rx->resets.rebase(c, tev.sample_counter); q.symbol_count = tev.symbol_count;
         q.len = tev.len; q.aux = tev.aux; q.aux2 = tev.aux2;
         q.n_bytes = std::min<uint32_t>(tev.len, SAME_EVENT_MAX_BYTES);
         if (tev.kind != SAME_TRANSPORT_MSG_START) q.n_bytes = 0;       // (only a header carries bytes)
@@ -612,7 +659,7 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
         const uint8_t *payload = nullptr;
         {
         HP(2);
-        q.kind = d.kind; q.channel = c; q.sample_counter = d.sample_counter; q.symbol_count = sym;
+        q.kind = d.kind; q.channel = c; q.sample_counter = rx->resets.rebase(c, d.sample_counter); q.symbol_count = sym;
         if (d.kind == SAME_LINK_BURST) {
             q.len = d.burst_len;
             if (d.burst_slot < n_bursts) {
@@ -887,6 +934,14 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     HarvestTimes times;
     int rc = harvest_host(rx, sl, n_events, n_bursts, rearm, times);
     if (rc) return rc;
+    // the harvest has reached the resets asked for behind this launch: their host half is due (before the wake table is
+    // re-armed below, so that a reset channel's entry goes back to the device as 0)
+    {
+        const int si = (int)(&sl - rx->slot);
+        const std::vector<uint32_t> &due = rx->resets.host_due(si);
+        for (uint32_t c : due) reset_channel_host(rx, c, rx->resets.rec_pos(si));
+        rx->resets.done_host(si);
+    }
     // force_eom_at_sample (receiver.rs:321-328) lives on the host; tell the device when to
     // wake the transport layer for it.  Launches are capped well below the 135 s timeout,
     // so the instant is always armed before the device reaches it.
@@ -1107,6 +1162,8 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         if (rc) return rc;
         // a launch continues the state the previous one leaves: on another stream than that one, wait for it
         if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
+        rc = launch_pending_resets(rx, sl, stream);
+        if (rc) return rc;
         same::ChunkGeom geom{};
         same::PipeChunks pc{};
         const uint32_t n_chunks = plan_chunks(rx, n, geom, pc);
@@ -1380,6 +1437,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     if (rc) return rc;
     // a launch continues the state the previous one leaves: on another stream than that one, wait for it
     if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
+    rc = launch_pending_resets(rx, sl, stream);
+    if (rc) return rc;
     rc = ensure_wide_state(rx, columns);
     if (rc) return rc;
     same::Output O{};
@@ -1692,6 +1751,7 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
 #undef TRY_OR_CLEAN
     if (!(flags & SAME_BATCH_LINK_ONLY)) { rx->thot.resize(n_channels); rx->tcold.resize(n_channels); }
     if (rx->tp.enabled) { rx->tp.sym_off.assign(n_channels, 0); rx->tp.synth.assign(n_channels, TickSynth{}); }
+    rx->resets.init(n_channels);
     *out = rx;
     return SAME_OK;
 }
@@ -1723,6 +1783,7 @@ void same_batch_free(same_batch *rx)
         if (sl.h_handover) (void)hipHostFree(sl.h_handover);
         if (sl.d_geom) (void)hipFree(sl.d_geom);
         if (sl.h_geom) (void)hipHostFree(sl.h_geom);
+        if (sl.h_reset) (void)hipHostFree(sl.h_reset);
     }
     if (rx->inv.d_buf) (void)hipFree(rx->inv.d_buf);
     if (rx->inv.ev_buf) (void)hipEventDestroy(rx->inv.ev_buf);
@@ -1766,9 +1827,40 @@ int same_batch_reset(same_batch *rx)
     for (auto &o : rx->tp.sym_off) o = 0;
     for (auto &t : rx->tp.synth) t.reset();
     if (rx->h_wake) std::memset(rx->h_wake, 0, (size_t)rx->P.n_channels * sizeof(uint64_t));
+    rx->resets.clear();                      // (per-channel resets still due are covered: every column was re-initialised)
     rx->overflowed = false;
     rx->kernel_fault = false;
     return SAME_OK;
+}
+
+int same_batch_reset_channels(same_batch *rx, const uint32_t *channels, size_t n)
+{
+    if (!rx) return fail(SAME_EINVAL, "null handle");
+    if (n && !channels) return fail(SAME_EINVAL, "null channel list");
+    if (!same::ResetLedger::normalise(channels, n, rx->P.n_channels, rx->reset_list))
+        return fail(SAME_EINVAL, "a channel of the list is out of range (the batch has %u); nothing was reset", rx->P.n_channels);
+    if (rx->reset_list.empty()) return SAME_OK;
+    HIP_TRY(hipSetDevice(rx->device));
+    if (rx->inv.on && rx->inv.fill) {
+        // SAME_BATCH_CALL_INVARIANT: what waits for its window is demodulated now and the next window begins at the reset, as
+        // behind a flush -- the reset's stream position fixes the launches around it, whatever the calls look like
+        const int rc = inv_launch_waiting(rx, rx->own_stream);
+        if (rc) return rc;
+    }
+    // the position is behind the newest launch; if the harvest has not reached it yet, the host half waits for that launch's
+    // harvest (no waiting here: it may still be running)
+    int newest = -1;
+    for (int s = 0; s < 2; ++s)
+        if (rx->slot[s].in_flight && (newest < 0 || rx->slot[s].seq > rx->slot[newest].seq)) newest = s;
+    rx->resets.request(rx->reset_list, rx->counter, newest, rx->reset_now);
+    for (uint32_t c : rx->reset_now) reset_channel_host(rx, c, rx->counter);
+    return SAME_OK;
+}
+
+uint64_t same_batch_channel_input_sample_counter(const same_batch *rx, uint32_t channel)
+{
+    if (!rx || channel >= rx->P.n_channels) return 0;
+    return rx->counter + rx->inv.fill - rx->resets.api_base[channel];
 }
 
 uint32_t same_batch_input_rate(const same_batch *rx) { return rx ? rx->P.input_rate : 0; }
@@ -2102,6 +2194,7 @@ long same_debug_harvest_replay(const char *path, int threads, int reps, double *
     rx->tp.enabled = h.tp_enabled != 0; rx->host_threads = threads;
     if (!(h.flags & SAME_BATCH_LINK_ONLY)) { rx->thot.resize(h.n_channels); rx->tcold.resize(h.n_channels); }
     if (rx->tp.enabled) { rx->tp.sym_off.assign(h.n_channels, 0); rx->tp.synth.assign(h.n_channels, TickSynth{}); }
+    rx->resets.init(h.n_channels);
     same_batch::Slot &sl = rx->slot[0];
     ev = ev0; hand = hand0;
     sl.h_sort = first.data(); sl.h_events = ev.data(); sl.h_bursts = bursts.data();

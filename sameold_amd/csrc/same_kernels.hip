@@ -181,11 +181,13 @@ __global__ __launch_bounds__(256) void transpose_to_time_major(const T *__restri
 // ---------------------------------------------------------------------------------
 // state initialisation: SameReceiver::from(&builder) receiver.rs:539-558 and reset() :182-198
 // ---------------------------------------------------------------------------------
-__global__ void init_state_kernel(Params P, State S, int is_reset, uint32_t first_col)
+// One state column.  Every kernel family reads its state from these arrays at a launch's start and leaves it there at the end
+// (the relaxed and symbol-paced kernels' squelch history, AGC and timing feedback included: State::sq_hist, agc_gain, flags), so
+// they are the whole receiver; fr_msg and the trace rows need no clearing (fr_len / trace_n say how much of them is valid).
+// Shared by the whole-batch initialisation / reset and by the per-channel reset, so the two cannot drift apart.
+__device__ __forceinline__ void init_state_column(const Params &P, const State &S, int is_reset, uint32_t c)
 {
-    const uint32_t c = first_col + blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t C = P.n_channels;
-    if (c >= C) return;
     for (uint32_t i = 0; i < P.dc_len; ++i) { S.dc_ff_ring[i * C + c] = 0.0f; S.dc_fb_ring[i * C + c] = 0.0f; }
     S.dc_sum0[c] = 0.0f; S.dc_sum1[c] = 0.0f;
     // Agc::new starts at min(1, min_gain) (rx/agc.rs:55) but reset() sets 1.0 (:61)
@@ -209,6 +211,22 @@ __global__ void init_state_kernel(Params P, State S, int is_reset, uint32_t firs
     S.tk_next[c] = kNoDeadline; S.tk_last[c] = kNoDeadline; S.tk_n[c] = 0; S.wake_sample[c] = 0; S.wake_fired[c] = 0;
     for (uint32_t i = 0; i < (uint32_t)kTickRing; ++i) S.tk_ring[i * C + c] = kNoDeadline;
     if (P.trace_cap) S.trace_n[c] = 0;
+}
+__global__ void init_state_kernel(Params P, State S, int is_reset, uint32_t first_col)
+{
+    const uint32_t c = first_col + blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= P.n_channels) return;
+    init_state_column(P, S, is_reset, c);
+}
+// SameReceiver::reset() (receiver.rs:182-198) of the listed channels only (same_batch_reset_channels): `cols` is a short list in
+// pinned host memory (ascending, unique, every entry < n_channels: the host checked), read once per thread
+__global__ __launch_bounds__(64) void reset_columns_kernel(Params P, State S, const uint32_t *__restrict__ cols, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t c = cols[i];
+    if (c >= P.n_channels) return;
+    init_state_column(P, S, 1, c);
 }
 
 // ---------------------------------------------------------------------------------
@@ -345,6 +363,13 @@ hipError_t launch_init_state(const Params &P, const State &S, int is_reset, hipS
     if (first_col >= P.n_channels) return hipSuccess;
     const uint32_t grid = (P.n_channels - first_col + 255) / 256;
     hipLaunchKernelGGL(init_state_kernel, dim3(grid), dim3(256), 0, stream, P, S, is_reset, first_col);
+    return hipGetLastError();
+}
+
+hipError_t launch_reset_columns(const Params &P, const State &S, const uint32_t *cols, uint32_t n, hipStream_t stream)
+{
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(reset_columns_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, S, cols, n);
     return hipGetLastError();
 }
 

@@ -65,6 +65,8 @@ hipError_t launch_event_sort(const DevEvent *ev, const uint32_t *counters, uint3
                              DevEvent *sorted, hipStream_t stream, bool cnt_is_zero = false);      // cnt_is_zero: the caller emptied cnt on this stream
 // (first_col: columns before it are left alone -- the time-parallel launches copy the channels' own state over them next)
 hipError_t launch_init_state(const Params &P, const State &S, int is_reset, hipStream_t stream, uint32_t first_col = 0);
+// reset() of the columns cols[0 .. n) (device-readable, e.g. mapped pinned host memory; each < P.n_channels)
+hipError_t launch_reset_columns(const Params &P, const State &S, const uint32_t *cols, uint32_t n, hipStream_t stream);
 // Column copies between state blobs of different widths: for every array of `desc` (device memory,
 // n_desc entries) and every column col < n_cols, dst[row][col] = src[row][src_col ? src_col[col] : col + src_base].
 hipError_t launch_copy_state_columns(const StateArrayDesc *desc, uint32_t n_desc, uint32_t src_channels,

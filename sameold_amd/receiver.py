@@ -164,6 +164,8 @@ def load_library() -> C.CDLL:
     sig("same_batch_new", C.c_int, vp, u32, C.c_int, u32, P(vp))
     sig("same_batch_free", None, vp)
     sig("same_batch_reset", C.c_int, vp)
+    sig("same_batch_reset_channels", C.c_int, vp, P(u32), C.c_size_t)
+    sig("same_batch_channel_input_sample_counter", u64, vp, u32)
     sig("same_batch_input_rate", u32, vp)
     sig("same_batch_n_channels", u32, vp)
     sig("same_batch_input_sample_counter", u64, vp)
@@ -362,6 +364,25 @@ class SameBatchReceiver:
 
     def reset(self):
         _check(self._L.same_batch_reset(self._h))
+
+    def reset_channels(self, channels) -> None:
+        """`SameReceiver::reset()` of some channels only (same_batch_reset_channels), at this point of the stream: behind the
+        samples of every call so far, ahead of the next call's.  `channels`: an int, a sequence, a numpy array or a CPU tensor.
+        Does not wait for the launches in flight; their events keep their numbering, and the reset channels' later events
+        count from 0.  An out-of-range channel raises SameError (EINVAL) and resets nothing."""
+        if hasattr(channels, "detach"):          # a torch tensor (CPU)
+            channels = channels.detach().numpy()
+        arr = np.atleast_1d(np.asarray(channels))
+        if arr.size and (arr.dtype.kind not in "iu" or arr.min() < 0 or arr.max() >= 1 << 32):
+            raise ValueError("channels must be non-negative integers")
+        arr = np.ascontiguousarray(arr.reshape(-1), dtype=np.uint32)
+        _check(self._L.same_batch_reset_channels(self._h, arr.ctypes.data_as(C.POINTER(C.c_uint32)), arr.size))
+
+    def channel_input_sample_counter(self, channel: int) -> int:
+        """`input_sample_counter()` of one channel: samples accepted since its last reset."""
+        if not 0 <= channel < self.n_channels:
+            raise IndexError(f"channel {channel} of {self.n_channels}")
+        return int(self._L.same_batch_channel_input_sample_counter(self._h, channel))
 
     def time_parallel_config(self, max_chunks: int = 0, min_own_samples: int = 0, warmup_samples: int = 0):
         """SAME_BATCH_TIME_PARALLEL tuning (0 = default), see include/same_rx.h."""
@@ -581,6 +602,59 @@ class SameReceiver:
         ev = Event()
         got = _check(self._L.same_rx_flush(self._h, C.byref(ev)))
         return ev.message() if got else None
+
+
+def decode_recordings(recordings: Sequence, input_rate: int, n_channels: int,
+                      builder: Optional[SameReceiverBuilder] = None, max_call_samples: Optional[int] = None,
+                      device: int = 0, **batch_flags) -> List[List[Event]]:
+    """Decode recordings of different lengths through one fixed batch of `n_channels` receivers.
+
+    Each recording (a 1-D int16 or float32 array of unscaled PCM at `input_rate`) gets a channel.  Behind its last sample the
+    channel is fed 4 * input_rate zeros (the reference's flush(), without stopping at the first message), the recording's
+    events are collected, and the channel is reset (`reset_channels`) and takes the next recording in the list, while the
+    other channels carry on.  Reset is the reference's reset(), not a fresh build(): a channel's second recording starts with
+    AGC gain 1.0 and with the equalizer and timing loop as the first one left them, as it would on one SameReceiver.  A channel without a recording is fed zeros.  Returns, per recording, its events, with sample
+    counters counted from the recording's own first sample.  `batch_flags` go to `build_batch` (relaxed=True, ...)."""
+    b = builder if builder is not None else SameReceiverBuilder(input_rate)
+    if b.input_rate() != input_rate:
+        raise ValueError(f"builder rate {b.input_rate()} != input_rate {input_rate}")
+    rx = b.build_batch(n_channels, device=device, **batch_flags)
+    step = int(max_call_samples) if max_call_samples else 2 * input_rate
+    tail = 4 * input_rate
+    tapes = [np.asarray(r).reshape(-1) for r in recordings]
+    out: List[List[Event]] = [[] for _ in tapes]
+    owner = [-1] * n_channels           # recording each channel decodes, -1 = none
+    pos = [0] * n_channels              # samples of its tape (recording + flush zeros) fed so far
+    nxt = 0
+    for c in range(n_channels):
+        if nxt < len(tapes):
+            owner[c] = nxt; nxt += 1
+    while any(o >= 0 for o in owner):
+        # a call ends where the first tape does: its channel is reset there, between two calls
+        left = [len(tapes[o]) + tail - pos[c] for c, o in enumerate(owner) if o >= 0]
+        n = min(step, min(left))
+        x = np.zeros((n, n_channels), dtype=np.float32)
+        for c, o in enumerate(owner):
+            if o < 0:
+                continue
+            t = tapes[o]
+            a, e = pos[c], min(pos[c] + n, len(t))
+            if a < e:
+                x[: e - a, c] = t[a:e]
+            pos[c] += n
+        rx.process_host(x)
+        for e in rx.poll_events():
+            o = owner[e.channel]
+            if o >= 0:
+                out[o].append(e)
+        done = [c for c, o in enumerate(owner) if o >= 0 and pos[c] == len(tapes[o]) + tail]
+        if done:
+            rx.reset_channels(done)
+            for c in done:
+                pos[c] = 0
+                owner[c] = nxt if nxt < len(tapes) else -1
+                nxt += nxt < len(tapes)
+    return out
 
 
 def synth_afsk(n_channels: int, n_samples: int, input_rate: int = 22050, seed: int = 1,
