@@ -213,7 +213,22 @@ enum {
      * SAME_BATCH_TIME_PARALLEL on a channel-major input are planned per call).  same_batch_input_sample_counter counts the
      * samples accepted, waiting ones included.  Cost: what of a call does not lie in whole windows is copied once (a call
      * shorter than a window is copied whole: one more pass over the input), and launches are a window long. */
-    SAME_BATCH_CALL_INVARIANT = 1u << 5
+    SAME_BATCH_CALL_INVARIANT = 1u << 5,
+    /* Messages only: the counterpart of iter_messages() (receiver.rs:155-161, filter_map(into_message_ok)).  The queue holds
+     * only SAME_TRANSPORT_MSG_START and SAME_TRANSPORT_MSG_END events -- exactly the ones iter_events() yields and
+     * iter_messages() keeps, with the sample_counter, symbol_count, len, aux, aux2 and header bytes a batch without the flag
+     * reports for them.  Link events, Idle, Assembling and MSG_ERR are not queued, and same_batch_pack_bursts counts 0 bursts.
+     * The transport layer (assembler, 2-of-3 combiner, header check) then runs on the device: a kernel behind every launch
+     * takes one channel per lane through the launch's link events (same_transport.hip), keeps the channels' transport state in
+     * HBM (about 1.8 KB per channel) and logs the messages, which are all that is copied back -- a launch's harvest replays
+     * nothing on the host.  The forced end of message is armed on the device as well.  Strict, SAME_BATCH_RELAXED,
+     * SAME_BATCH_CALL_INVARIANT, int16 and both layouts, same_batch_flush, same_batch_reset and same_batch_reset_channels
+     * (the reset re-initialises the channels' transport state in front of the next launch: the same position) all work as
+     * without the flag.  A SAME_BATCH_TIME_PARALLEL batch keeps its stitch and transport layer on the host, which need the
+     * chunked stream whole: it queues only the messages too, and same_batch_transport_on_device says 0.  A message log that
+     * fills up truncates the results and the call returns SAME_EOVERFLOW, as an event log does.  Not combinable with
+     * SAME_BATCH_LINK_ONLY (SAME_EINVAL). */
+    SAME_BATCH_MESSAGES_ONLY = 1u << 6
 };
 #define SAME_TP_EVENT_TOLERANCE_SYMBOLS 2
 
@@ -319,7 +334,8 @@ int same_batch_drop_events(same_batch *rx, size_t n);
 /* The queued SAME_LINK_BURST events as fixed 304-byte records, in queue order: u32 channel +
  * first_channel, u64 sample_counter, u32 length (<= 288), 288 payload bytes zero-padded (the record
  * the multi-GPU gather moves, sameold_amd/distributed.py).  out == NULL: only counts.  Writes at most
- * `cap` records; *n_records = bursts queued.  The queue is left as it is. */
+ * `cap` records; *n_records = bursts queued.  The queue is left as it is.  A SAME_BATCH_MESSAGES_ONLY
+ * batch queues no bursts: *n_records is 0. */
 #define SAME_BURST_RECORD_BYTES 304
 int same_batch_pack_bursts(same_batch *rx, uint32_t first_channel, uint8_t *out, size_t cap, size_t *n_records);
 
@@ -335,6 +351,9 @@ uint32_t same_batch_time_parallel_chunks(const same_batch *rx);
  * 64-channel workgroups.  Such a call reads the input where it lies (no transposition pass); its chunks seldom
  * run on, so it is the faster form of the mode. */
 int same_batch_time_parallel_per_channel(const same_batch *rx);
+
+/* 1 when the last process call's transport layer ran on the device (SAME_BATCH_MESSAGES_ONLY, not time-parallel), else 0 */
+int same_batch_transport_on_device(const same_batch *rx);
 
 /* soft-symbol trace (SAME_BATCH_TRACE_SYMBOLS): SymbolEstimate stream of one channel
  * (rx/symsync.rs:52-71) with the input sample counter of each TED instant */

@@ -250,6 +250,12 @@ struct same_batch {
         // channels re-initialised in front of this launch (same_batch_reset_channels): pinned, mapped, read by the reset kernel
         uint32_t *h_reset = nullptr, *h_reset_dev = nullptr;
         uint32_t reset_cap = 0;
+        // SAME_BATCH_MESSAGES_ONLY: the launch's message log (same_transport.hip; its cursor is d_counters[3]) and its landing buffer
+        bool dev_transport = false;      // this launch ran the transport layer on the device
+        // (its first records land in host-mapped pinned memory, read in place; the rest in HBM, copied when there are any)
+        same::DevMessage *h_near = nullptr, *h_near_dev = nullptr; uint32_t near_cap = 0;
+        same::DevMessage *d_msgs = nullptr; uint32_t msg_cap = 0;
+        void *h_msgs = nullptr; size_t h_msgs_bytes = 0;
     } slot[2];
     // time-parallel mode (SAME_BATCH_TIME_PARALLEL)
     struct TimePar {
@@ -340,6 +346,12 @@ struct same_batch {
     std::vector<same::TransportCold> tcold;
     same::TransportRef tr(uint32_t c) { return same::TransportRef(thot[c], tcold[c]); }
     uint64_t *h_wake = nullptr;      // host mirror of State::wake_sample (pinned, n_channels words, zero = unarmed)
+    // SAME_BATCH_MESSAGES_ONLY: only MSG_START / MSG_END are queued; unless the batch is time-parallel the transport layer runs on
+    // the device (same_transport.hip) over per-channel records in HBM, and the device arms State::wake_sample itself
+    bool messages_only = false;
+    bool dev_transport = false;
+    bool last_dev_transport = false; // the last process call's launches ran it there (same_batch_transport_on_device)
+    void *d_thot = nullptr, *d_tcold = nullptr;
     // per-channel resets (same_batch_reset_channels): where each half of a reset is due, the channels' counter bases
     same::ResetLedger resets;
     std::vector<uint32_t> reset_list, reset_now, reset_cols;       // scratch: the entry point's, the reset kernel's list
@@ -468,6 +480,24 @@ int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::
         HIP_TRY(hipMalloc((void **)&sl.d_bursts, bcap * same::kBurstCap));
         sl.burst_cap = (uint32_t)bcap;
     }
+    if (rx->dev_transport && !n_columns) {
+        // a message needs a burst, except a pending one from an earlier launch and a forced end of message: two per channel more
+        const size_t mcap = std::min<size_t>(bcap + 2 * n_ch, 0x7fffffffu / sizeof(same::DevMessage));
+        if (mcap > sl.msg_cap) {
+            if (sl.d_msgs) HIP_TRY(hipFree(sl.d_msgs));
+            sl.d_msgs = nullptr; sl.msg_cap = 0;
+            HIP_TRY(hipMalloc((void **)&sl.d_msgs, mcap * sizeof(same::DevMessage)));
+            sl.msg_cap = (uint32_t)mcap;
+        }
+        if (!sl.h_near) {
+            // (a copy of a few kilobytes beside a launch that fills the machine waits for that launch: measured 2.7 ms at the
+            // 32 768-channel shard, the host spinning on it; writes into mapped memory need no copy)
+            const uint32_t want = std::max<uint32_t>(4096u, (uint32_t)(n_ch / 4u));
+            HIP_TRY(hipHostMalloc((void **)&sl.h_near, (size_t)want * sizeof(same::DevMessage), hipHostMallocMapped | hipHostMallocCoherent));
+            HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_near_dev, sl.h_near, 0));
+            sl.near_cap = want;
+        }
+    }
     {
         const size_t need = 2 * n_ch + 1 + same::event_sort_extra_words((uint32_t)n_ch), need_h = n_ch + 1;
         if (sl.event_cap > sl.sorted_cap) {
@@ -562,7 +592,9 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
         sl.reset_cap = want;
     }
     std::memcpy(sl.h_reset, cols.data(), (size_t)n * sizeof(uint32_t));
-    const hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset_dev, n, stream);
+    hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset_dev, n, stream);
+    // (SAME_BATCH_MESSAGES_ONLY: the transport layer lives on the device, and is reset there at the same position)
+    if (e == hipSuccess && rx->dev_transport) e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, sl.h_reset_dev, n, 0, stream);
     if (e != hipSuccess) return fail(SAME_EHIP, "channel reset launch failed: %s", hipGetErrorString(e));
     return SAME_OK;
 }
@@ -570,6 +602,22 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
 // The host half of a harvest: the launch's ordered event log, burst pool, hand-over instants and chunk geometry are in the
 // slot's host buffers; order each column's records, replay the channels (stitch + transport layer) on the worker threads and
 // append to the queue.  Touches no device: same_debug_harvest_replay runs it on a recorded launch without one.
+// Before a harvest appends to the queue.  A consumer that always polls less than is pending never drains the queue: reclaim the
+// polled prefix once it is at least as large as what is still waiting (amortised O(1) per event).
+void prepare_queue_append(same_batch *rx)
+{
+    rx->peeked_valid = false;                 // (the queue is about to move and grow: a materialised view of it is stale)
+    release_stale_view(rx);
+    if (rx->queue_head && rx->queue_head >= rx->queue.size() - rx->queue_head) {
+        rx->queue_head = rx->queue.compact(rx->queue_head);
+        // ... and the payload bytes in front of the first record that is still queued
+        size_t keep_from = rx->arena.base + rx->arena.size();
+        for (size_t i = 0; i < rx->queue.size(); ++i)
+            if (rx->queue.data()[i].n_bytes) { keep_from = (size_t)rx->queue.data()[i].payload; break; }
+        rx->arena.compact(keep_from - rx->arena.base);
+    }
+}
+
 struct HarvestTimes { std::chrono::steady_clock::time_point sorted, replayed; uint32_t n_threads = 1; };
 int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, std::vector<uint32_t> &rearm, HarvestTimes &times)
 {
@@ -636,7 +684,9 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     // (transport events arrive as same_rx_event from the transport layer: kept as a record + payload)
     // (the stitch and the transport layer work on the device's counters, from the batch's first sample; a queue record counts
     // from its channel's last reset: same_batch_reset_channels)
+    const bool msgs_only = rx->messages_only;
     auto push_transport = [&](Part &part, const same_rx_event &tev, uint32_t c) {
+        if (msgs_only && tev.kind != SAME_TRANSPORT_MSG_START && tev.kind != SAME_TRANSPORT_MSG_END) return;
         QEvent q{};
         q.kind = tev.kind; q.channel = c; q.sample_counter = rx->resets.rebase(c, tev.sample_counter); q.symbol_count = tev.symbol_count;
         q.len = tev.len; q.aux = tev.aux; q.aux2 = tev.aux2;
@@ -666,13 +716,13 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
                 q.n_bytes = std::min<uint32_t>(d.burst_len, SAME_EVENT_MAX_BYTES);
                 payload = bursts + (size_t)d.burst_slot * same::kBurstCap;
                 q.payload = part.bytes.size();
-                part.bytes.insert(part.bytes.end(), payload, payload + q.n_bytes);
+                if (!msgs_only) part.bytes.insert(part.bytes.end(), payload, payload + q.n_bytes);
             } else {
                 q.len = 0;     // pool overflow: the burst bytes were lost (SAME_EOVERFLOW is reported)
             }
-            part.bursts.push_back((uint32_t)part.out.size());
+            if (!msgs_only) part.bursts.push_back((uint32_t)part.out.size());
         }
-        if (d.kind <= SAME_LINK_BURST) part.out.push_back(q);
+        if (d.kind <= SAME_LINK_BURST && !msgs_only) part.out.push_back(q);
         }
         if (!link_only) {
 #ifdef SAME_HOST_PROF
@@ -829,18 +879,7 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     times.n_threads = n_threads;
     size_t total = 0, total_bytes = 0;
     for (const Part &p : parts) { total += p.out.size(); total_bytes += p.bytes.size(); }
-    // a consumer that always polls less than is pending never drains the queue: reclaim the polled
-    // prefix once it is at least as large as what is still waiting (amortised O(1) per event)
-    rx->peeked_valid = false;                 // (the queue is about to move and grow: a materialised view of it is stale)
-    release_stale_view(rx);
-    if (rx->queue_head && rx->queue_head >= rx->queue.size() - rx->queue_head) {
-        rx->queue_head = rx->queue.compact(rx->queue_head);
-        // ... and the payload bytes in front of the first record that is still queued
-        size_t keep_from = rx->arena.base + rx->arena.size();
-        for (size_t i = 0; i < rx->queue.size(); ++i)
-            if (rx->queue.data()[i].n_bytes) { keep_from = (size_t)rx->queue.data()[i].payload; break; }
-        rx->arena.compact(keep_from - rx->arena.base);
-    }
+    prepare_queue_append(rx);
     QEvent *dst = rx->queue.grow(total);
     if (total && !dst) return fail(SAME_ENOMEM, "event queue");
     uint8_t *bdst = rx->arena.grow(total_bytes);
@@ -876,6 +915,76 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
 
 int record_harvest(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, const char *path);
 
+// a pinned landing buffer of at least `need` bytes
+hipError_t grow_pinned(void **p, size_t *have, size_t need)
+{
+    if (need <= *have) return hipSuccess;
+    if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
+    const size_t want = need + need / 2 + 4096;
+    hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
+    if (e == hipSuccess) *have = want;
+    return e;
+}
+
+// The harvest of a launch that ran the transport layer on the device (SAME_BATCH_MESSAGES_ONLY): its message log is all that
+// comes back -- no event log, no burst pool, no replay.  The log's order across lanes is that of their atomics; the queue
+// takes it by channel and, per channel, in the order the lane logged it (= iter_events() filtered to messages).
+int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_clock::time_point t_begin,
+                     std::chrono::steady_clock::time_point t_waited)
+{
+    const uint32_t n_msgs = std::min(sl.h_counters[3], sl.near_cap + sl.msg_cap);
+    const uint32_t n_near = std::min(n_msgs, sl.near_cap), n_far = n_msgs - n_near;
+    const size_t far_bytes = (size_t)n_far * sizeof(same::DevMessage);
+    if (n_far) {
+        HIP_TRY(grow_pinned(&sl.h_msgs, &sl.h_msgs_bytes, far_bytes));
+        HIP_TRY(hipMemcpyAsync(sl.h_msgs, sl.d_msgs, far_bytes, hipMemcpyDeviceToHost, rx->copy_stream));
+        HIP_TRY(hipStreamSynchronize(rx->copy_stream));
+    }
+    auto t_copied = std::chrono::steady_clock::now();
+    const same::DevMessage *far = static_cast<const same::DevMessage *>(sl.h_msgs);
+    auto rec = [&](uint32_t i) -> const same::DevMessage & { return i < n_near ? sl.h_near[i] : far[i - n_near]; };
+    std::vector<uint32_t> order(n_msgs);
+    size_t n_bytes = 0;
+    for (uint32_t i = 0; i < n_msgs; ++i) {
+        order[i] = i;
+        if (rec(i).kind == SAME_TRANSPORT_MSG_START) n_bytes += std::min<uint32_t>(rec(i).len, same::kDevMessageText);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const same::DevMessage &x = rec(a), &y = rec(b);
+        return x.channel != y.channel ? x.channel < y.channel : x.seq < y.seq;
+    });
+    prepare_queue_append(rx);
+    QEvent *dst = rx->queue.grow(n_msgs);
+    if (n_msgs && !dst) return fail(SAME_ENOMEM, "event queue");
+    uint8_t *bdst = rx->arena.grow(n_bytes);
+    if (n_bytes && !bdst) return fail(SAME_ENOMEM, "event payloads");
+    size_t at = n_bytes ? rx->arena.base + (size_t)(bdst - rx->arena.data()) : 0;
+    for (uint32_t k = 0; k < n_msgs; ++k) {
+        const same::DevMessage &d = rec(order[k]);
+        QEvent q{};
+        q.kind = d.kind; q.channel = d.channel; q.sample_counter = rx->resets.rebase(d.channel, d.sample_counter);
+        q.symbol_count = d.symbol_count; q.len = d.len; q.aux = d.aux; q.aux2 = d.aux2;
+        if (d.kind == SAME_TRANSPORT_MSG_START && d.len) {
+            q.n_bytes = std::min<uint32_t>(d.len, same::kDevMessageText);
+            q.payload = at;
+            std::memcpy(bdst, d.text, q.n_bytes);
+            bdst += q.n_bytes; at += q.n_bytes;
+        }
+        dst[k] = q;
+    }
+    // the harvest has reached the resets asked for behind this launch: their host half (the counter bases) is due
+    const int si = (int)(&sl - rx->slot);
+    for (uint32_t c : rx->resets.host_due(si)) reset_channel_host(rx, c, rx->resets.rec_pos(si));
+    rx->resets.done_host(si);
+    if (rx->debug) {
+        auto t_end = std::chrono::steady_clock::now();
+        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr, "[same] harvest timing: wait %.2f ms, copy %.2f ms, %u messages queued in %.2f ms (transport layer on the device)\n",
+                     ms(t_begin, t_waited), ms(t_waited, t_copied), n_msgs, ms(t_copied, t_end));
+    }
+    return SAME_OK;
+}
+
 // Collect the finished launch (device half): wait for it, copy its ordered log, burst pool and geometry back
 int harvest_slot(same_batch *rx, same_batch::Slot &sl)
 {
@@ -898,19 +1007,12 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
         std::fprintf(stderr, "[same] harvest: %u device events (%u bursts), cap %u/%u\n", sl.h_counters[0],
                      sl.h_counters[1], sl.event_cap, sl.burst_cap);
     const uint32_t n_bursts = std::min(sl.h_counters[1], sl.burst_cap);
-    if (sl.h_counters[2] & 3u) rx->overflowed = true;
+    if (sl.h_counters[2] & (3u | same::kMessageLogOverflow)) rx->overflowed = true;
     if (sl.h_counters[2] & 4u) rx->kernel_fault = true;
+    if (sl.dev_transport) return harvest_messages(rx, sl, t_begin, t_waited);
     const size_t ev_bytes = (size_t)n_events * sizeof(same::DevEvent), bu_bytes = (size_t)n_bursts * same::kBurstCap;
-    auto grow = [](void **p, size_t *have, size_t need) -> hipError_t {
-        if (need <= *have) return hipSuccess;
-        if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-        const size_t want = need + need / 2 + 4096;
-        hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
-        if (e == hipSuccess) *have = want;
-        return e;
-    };
-    HIP_TRY(grow(&sl.h_events, &sl.h_events_bytes, ev_bytes));
-    HIP_TRY(grow(&sl.h_bursts, &sl.h_bursts_bytes, bu_bytes));
+    HIP_TRY(grow_pinned(&sl.h_events, &sl.h_events_bytes, ev_bytes));
+    HIP_TRY(grow_pinned(&sl.h_bursts, &sl.h_bursts_bytes, bu_bytes));
     // the event log first: it is what the sort below needs, and the sort runs while the burst pool (the larger copy) and
     // the chunk geometry are still on their way
     const uint32_t n_ch = rx->P.n_channels;
@@ -1286,6 +1388,20 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
         HIP_TRY(same::launch_event_sort(sl.d_events, sl.d_counters, sl.event_cap, sl.sort_bins, sl.d_sort, sl.d_sort + sl.sort_bins,
                                         sl.d_sorted, stream, sort_bins_empty));
+        // SAME_BATCH_MESSAGES_ONLY: the transport layer over the ordered log, a lane per channel, on the launch's stream (the next
+        // launch, which reads the forced-EOM instants it arms, is ordered behind it)
+        sl.dev_transport = rx->dev_transport && !sl.chunked;
+        rx->last_dev_transport = sl.dev_transport;
+        if (sl.dev_transport) {
+            same::TransportLaunch T{};
+            T.n_channels = rx->P.n_channels; T.input_rate = rx->P.input_rate;
+            T.first = sl.d_sort + sl.sort_bins; T.sorted = sl.d_sorted; T.counters = sl.d_counters;
+            T.bursts = sl.d_bursts; T.burst_cap = sl.burst_cap;
+            T.hot = rx->d_thot; T.cold = rx->d_tcold; T.wake_sample = rx->S.wake_sample;
+            T.near = sl.h_near_dev; T.near_cap = sl.near_cap;
+            T.log = sl.d_msgs; T.log_cap = sl.msg_cap; T.log_cursor = sl.d_counters + 3; T.overflow = sl.d_counters + 2;
+            HIP_TRY(same::launch_transport(T, stream));
+        }
         HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 1, stream));
         HIP_TRY(hipEventRecord(sl.ev_done, stream));
         sl.in_flight = true;
@@ -1558,6 +1674,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
         if (e2 != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e2));
     }
     sl.chunked = true; sl.per_channel = true;
+    sl.dev_transport = false;
+    rx->last_dev_transport = false;
     sl.geom = geom;
     sl.end_blocks = rx->counter + n;
     if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
@@ -1693,7 +1811,13 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
         delete rx;
         return fail(SAME_EINVAL, "SAME_BATCH_TIME_PARALLEL cannot record a symbol trace");
     }
+    if ((flags & SAME_BATCH_MESSAGES_ONLY) && (flags & SAME_BATCH_LINK_ONLY)) {
+        delete rx;
+        return fail(SAME_EINVAL, "SAME_BATCH_MESSAGES_ONLY needs the transport layer that SAME_BATCH_LINK_ONLY skips");
+    }
     rx->tp.enabled = (flags & SAME_BATCH_TIME_PARALLEL) != 0;
+    rx->messages_only = (flags & SAME_BATCH_MESSAGES_ONLY) != 0;
+    rx->dev_transport = rx->messages_only && !rx->tp.enabled;      // (time-parallel: the stitch needs the transport layer on the host)
     // transport wake-ups come from the device in strict mode, from the host's symbol clock in time-parallel mode
     rx->P.ticks = ((flags & SAME_BATCH_LINK_ONLY) || rx->tp.enabled) ? 0u : 1u;
     rx->P.tick_interburst = (uint32_t)same::max_interburst_symbols();
@@ -1747,9 +1871,16 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
     TRY_OR_CLEAN(hipMemset(rx->d_state_blob, 0, rx->state_bytes));
     carve_state(rx->P, (char *)rx->d_state_blob, rx->S);
     TRY_OR_CLEAN(same::launch_init_state(rx->P, rx->S, 0, rx->own_stream));
+    if (rx->dev_transport) {
+        // the transport layer's per-channel records in HBM: a hot line and a cold record each (same_transport_dev.h)
+        TRY_OR_CLEAN(hipMalloc(&rx->d_thot, (size_t)n_channels * same::transport_hot_bytes()));
+        TRY_OR_CLEAN(hipMalloc(&rx->d_tcold, (size_t)n_channels * same::transport_cold_bytes()));
+        TRY_OR_CLEAN(hipMemsetAsync(rx->d_tcold, 0, (size_t)n_channels * same::transport_cold_bytes(), rx->own_stream));
+        TRY_OR_CLEAN(same::launch_transport_reset(rx->d_thot, rx->d_tcold, n_channels, nullptr, 0, 1, rx->own_stream));
+    }
     TRY_OR_CLEAN(hipStreamSynchronize(rx->own_stream));
 #undef TRY_OR_CLEAN
-    if (!(flags & SAME_BATCH_LINK_ONLY)) { rx->thot.resize(n_channels); rx->tcold.resize(n_channels); }
+    if (!(flags & SAME_BATCH_LINK_ONLY) && !rx->dev_transport) { rx->thot.resize(n_channels); rx->tcold.resize(n_channels); }
     if (rx->tp.enabled) { rx->tp.sym_off.assign(n_channels, 0); rx->tp.synth.assign(n_channels, TickSynth{}); }
     rx->resets.init(n_channels);
     *out = rx;
@@ -1784,7 +1915,12 @@ void same_batch_free(same_batch *rx)
         if (sl.d_geom) (void)hipFree(sl.d_geom);
         if (sl.h_geom) (void)hipHostFree(sl.h_geom);
         if (sl.h_reset) (void)hipHostFree(sl.h_reset);
+        if (sl.d_msgs) (void)hipFree(sl.d_msgs);
+        if (sl.h_near) (void)hipHostFree(sl.h_near);
+        if (sl.h_msgs) (void)hipHostFree(sl.h_msgs);
     }
+    if (rx->d_thot) (void)hipFree(rx->d_thot);
+    if (rx->d_tcold) (void)hipFree(rx->d_tcold);
     if (rx->inv.d_buf) (void)hipFree(rx->inv.d_buf);
     if (rx->inv.ev_buf) (void)hipEventDestroy(rx->inv.ev_buf);
     if (rx->tp.blob) (void)hipFree(rx->tp.blob);
@@ -1814,6 +1950,7 @@ int same_batch_reset(same_batch *rx)
     int rc = harvest(rx);
     if (rc) return rc;
     hipError_t e = same::launch_init_state(rx->P, rx->S, 1, rx->own_stream);
+    if (e == hipSuccess && rx->dev_transport) e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, nullptr, 0, 0, rx->own_stream);
     if (e != hipSuccess) return fail(SAME_EHIP, "reset launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(rx->own_stream));
     rx->counter = 0;
@@ -2115,6 +2252,7 @@ int same_batch_time_parallel_config(same_batch *rx, uint32_t max_chunks, uint32_
     return SAME_OK;
 }
 uint32_t same_batch_time_parallel_chunks(const same_batch *rx) { return rx ? rx->tp.last_chunks : 0; }
+int same_batch_transport_on_device(const same_batch *rx) { return rx && rx->last_dev_transport ? 1 : 0; }
 int same_batch_time_parallel_per_channel(const same_batch *rx) { return rx && rx->tp.last_chunks > 1u && rx->tp.last_per_channel ? 1 : 0; }
 
 const char *same_batch_kernel_name(const same_batch *rx)

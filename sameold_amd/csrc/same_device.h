@@ -195,6 +195,20 @@ struct DevEvent {
     uint32_t burst_slot;     // index into the burst pool, 0xffffffff = none
 };
 
+// One transport message as the device transport layer logs it (SAME_BATCH_MESSAGES_ONLY, same_transport.hip): a
+// SAME_TRANSPORT_MSG_START / _END event of a channel, `seq` numbering the channel's messages inside the launch (the log's
+// order across lanes is that of their atomics).  312 bytes.
+constexpr uint32_t kDevMessageText = 272;        // >= MAX_MESSAGE_LENGTH 268 (rx/assembler.rs:70)
+struct DevMessage {
+    uint32_t channel;
+    uint32_t kind;           // SAME_TRANSPORT_MSG_START / _END
+    uint64_t sample_counter;
+    uint64_t symbol_count;
+    uint32_t len, aux, aux2; // as same_rx_event
+    uint32_t seq;
+    uint8_t text[kDevMessageText];   // MSG_START: the header's len bytes
+};
+
 // Append-only output of one launch.
 struct Output {
     DevEvent *events;

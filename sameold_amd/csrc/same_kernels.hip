@@ -234,9 +234,10 @@ __global__ __launch_bounds__(64) void reset_columns_kernel(Params P, State S, co
 // device-to-host copy in the stream drags the SDMA engine and host-resolved dependencies
 // between consecutive launches into the critical path)
 // ---------------------------------------------------------------------------------
+// (four words: [0] events [1] bursts [2] overflow [3] messages of the device transport layer; both buffers hold four)
 __global__ void counters_kernel(uint32_t *dev, volatile uint32_t *host, int publish)
 {
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 4) {
         if (publish) host[threadIdx.x] = dev[threadIdx.x];
         else dev[threadIdx.x] = 0;
     }

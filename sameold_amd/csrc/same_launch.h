@@ -103,6 +103,32 @@ hipError_t launch_transpose_f32(const float *in, float *out, uint32_t n_channels
 hipError_t launch_transpose_i16(const int16_t *in, int16_t *out, uint32_t n_channels, uint32_t n_samples,
                                 hipStream_t stream);
 
+// The transport layer on the device (same_transport.hip, SAME_BATCH_MESSAGES_ONLY): one lane per channel walks its range of
+// the launch's column-ordered log (behind launch_event_sort), runs the transport layer over it and appends the messages to
+// the log: records 0 .. near_cap - 1 go to `near` (host-mapped pinned memory the host reads in place: a launch's few hundred
+// messages need no copy), the rest to `log` (HBM); a full log sets kMessageLogOverflow in *overflow.  hot / cold: n_channels records of transport_hot_bytes() /
+// transport_cold_bytes() (same_transport_dev.h).
+constexpr uint32_t kMessageLogOverflow = 8u;      // bit of the launch's overflow word (1: event log, 2: burst pool)
+struct TransportLaunch {
+    uint32_t n_channels, input_rate;
+    const uint32_t *first;         // [n_channels + 1] the columns' ranges of `sorted`
+    DevEvent *sorted;              // re-ordered in place, range by range
+    const uint32_t *counters;      // the launch's cursors: [1] bursts logged
+    const uint8_t *bursts; uint32_t burst_cap;
+    void *hot, *cold;
+    uint64_t *wake_sample;         // State::wake_sample: the forced-EOM instant the next launch wakes the channel after
+    DevMessage *near; uint32_t near_cap;
+    DevMessage *log; uint32_t log_cap;
+    uint32_t *log_cursor, *overflow;
+};
+size_t transport_hot_bytes();
+size_t transport_cold_bytes();
+hipError_t launch_transport(const TransportLaunch &T, hipStream_t stream);
+// reset() of the transport layer of the columns cols[0 .. n) (device-readable), or of every channel (cols == nullptr); fresh: the
+// records were never written (a new batch)
+hipError_t launch_transport_reset(void *hot, void *cold, uint32_t n_channels, const uint32_t *cols, uint32_t n, int fresh,
+                                  hipStream_t stream);
+
 // synthetic workload (same_synth.hip)
 struct SynthParams {
     uint32_t n_channels;

@@ -27,6 +27,7 @@ LINK_NO_CARRIER, LINK_SEARCHING, LINK_READING, LINK_BURST = 0, 1, 2, 3
 TRANSPORT_IDLE, TRANSPORT_ASSEMBLING, TRANSPORT_MSG_START, TRANSPORT_MSG_END, TRANSPORT_MSG_ERR = 16, 17, 18, 19, 20
 LAYOUT_TIME_MAJOR, LAYOUT_CHANNEL_MAJOR = 0, 1
 BATCH_LINK_ONLY, BATCH_TRACE_SYMBOLS, BATCH_GENERIC_KERNEL, BATCH_TIME_PARALLEL, BATCH_RELAXED, BATCH_CALL_INVARIANT = 1, 2, 4, 8, 16, 32
+BATCH_MESSAGES_ONLY = 64            # SAME_BATCH_MESSAGES_ONLY: only MSG_START / MSG_END are queued (iter_messages())
 TP_EVENT_TOLERANCE_SYMBOLS = 2      # SAME_TP_EVENT_TOLERANCE_SYMBOLS
 STREAM_OWN = (1 << 64) - 1          # SAME_STREAM_OWN: (void *)-1, the library's own stream
 EVENT_MAX_BYTES = 288
@@ -176,6 +177,7 @@ def load_library() -> C.CDLL:
     sig("same_batch_time_parallel_config", C.c_int, vp, u32, u32, u32)
     sig("same_batch_time_parallel_chunks", u32, vp)
     sig("same_batch_time_parallel_per_channel", C.c_int, vp)
+    sig("same_batch_transport_on_device", C.c_int, vp)
     sig("same_rx_source_hash", C.c_char_p)
     sig("same_batch_process_device_i16", C.c_int, vp, vp, C.c_size_t, u32, vp)
     sig("same_batch_process_host", C.c_int, vp, vp, C.c_size_t, u32)
@@ -318,11 +320,14 @@ class SameReceiverBuilder:
 
     def build_batch(self, n_channels: int, device: int = 0, link_only: bool = False,
                     trace_symbols: bool = False, generic_kernel: bool = False,
-                    time_parallel: bool = False, relaxed: bool = False, call_invariant: bool = False) -> "SameBatchReceiver":
+                    time_parallel: bool = False, relaxed: bool = False, call_invariant: bool = False,
+                    messages_only: bool = False) -> "SameBatchReceiver":
         """call_invariant (SAME_BATCH_CALL_INVARIANT): the stream is demodulated in windows that begin at fixed stream positions,
         so the events do not depend on how it is cut into calls (they arrive when a window's last sample has; flush() brings in
-        what is waiting)."""
-        return SameBatchReceiver(self, n_channels, device, link_only, trace_symbols, generic_kernel, time_parallel, relaxed, call_invariant)
+        what is waiting).  messages_only (SAME_BATCH_MESSAGES_ONLY): the counterpart of iter_messages() -- only the
+        StartOfMessage / EndOfMessage events are queued, and the transport layer runs on the device."""
+        return SameBatchReceiver(self, n_channels, device, link_only, trace_symbols, generic_kernel, time_parallel, relaxed, call_invariant,
+                                 messages_only)
 
 
 class SameBatchReceiver:
@@ -330,12 +335,13 @@ class SameBatchReceiver:
 
     def __init__(self, builder: SameReceiverBuilder, n_channels: int, device: int = 0,
                  link_only: bool = False, trace_symbols: bool = False, generic_kernel: bool = False,
-                 time_parallel: bool = False, relaxed: bool = False, call_invariant: bool = False):
+                 time_parallel: bool = False, relaxed: bool = False, call_invariant: bool = False, messages_only: bool = False):
         self._L = load_library()
         h = C.c_void_p()
         flags = ((BATCH_LINK_ONLY if link_only else 0) | (BATCH_TRACE_SYMBOLS if trace_symbols else 0)
                  | (BATCH_GENERIC_KERNEL if generic_kernel else 0) | (BATCH_TIME_PARALLEL if time_parallel else 0)
-                 | (BATCH_RELAXED if relaxed else 0) | (BATCH_CALL_INVARIANT if call_invariant else 0))
+                 | (BATCH_RELAXED if relaxed else 0) | (BATCH_CALL_INVARIANT if call_invariant else 0)
+                 | (BATCH_MESSAGES_ONLY if messages_only else 0))
         _check(self._L.same_batch_new(builder._h, n_channels, device, flags, C.byref(h)))
         self._h = h
         self._inflight = []          # input tensors of launches that may still be running (process_tensor)
@@ -391,6 +397,10 @@ class SameBatchReceiver:
     def time_parallel_chunks(self) -> int:
         """Chunks per channel of the most recent process call (1 = one strict launch)."""
         return self._L.same_batch_time_parallel_chunks(self._h)
+
+    def transport_on_device(self) -> int:
+        """1 when the last process call's transport layer ran on the device (messages_only, not time-parallel), else 0."""
+        return int(self._L.same_batch_transport_on_device(self._h))
 
     def time_parallel_per_channel(self) -> bool:
         """Whether that call's chunk boundaries were chosen per channel (channel-major input, see same_rx.h)."""
