@@ -287,6 +287,10 @@ int same_batch_device(const same_batch *rx);
  * same_batch_sync returns, or until the second-next process call on this handle returns
  * (at most two launches are in flight; a process call collects the launch before the
  * previous one).  A caching allocator must not be allowed to reuse the buffer earlier.
+ * The same holds under SAME_BATCH_CALL_INVARIANT, where a call may only copy its samples
+ * into the waiting buffer: a process call -- a short one too -- may block until the reads of
+ * the call before the previous one are done, and same_batch_sync waits for the reads of
+ * every call.  same_batch_process_host reuses its upload buffer only after those reads.
  * Successive launches of one batch are ordered among themselves whatever streams they are
  * given: a launch continues the state the previous one leaves, and waits for it. */
 #define SAME_STREAM_OWN ((void *)(intptr_t)-1)

@@ -299,6 +299,11 @@ struct same_batch {
         void *d_buf = nullptr; size_t buf_bytes = 0;
         hipEvent_t ev_buf = nullptr;   // behind the last operation on d_buf (a later call may come on another stream)
         hipStream_t buf_stream = nullptr; bool buf_used = false;
+        // behind the last operation of each of the two latest process calls that read the caller's buffer (or the batch's
+        // staging / upload buffers): call k waits for call k - 2's before it returns (inv_reads_end)
+        hipEvent_t ev_read[2] = {nullptr, nullptr};
+        uint64_t n_reads = 0;          // process calls so far; the latest one's event is ev_read[(n_reads - 1) & 1]
+        hipStream_t read_stream = nullptr;
     } inv;
     // Time-parallel launches on the library's own stream: scout, planner and sort of call k + 1 run here, beside the tail of
     // launch k (whose short workgroups have left their CUs by then); the own stream waits for them (Slot::ev_planned)
@@ -1289,9 +1294,18 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             sl.timed = rx->timing; if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_start, stream));
             // fresh receivers in every column (with the hand-over records, the event sort's bins and the launch cursors: one
             // kernel), then the channels' own state into chunk 0's columns
-            HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
+            if (tp.knob_prologue >= 0) {
+                HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
+                sort_bins_empty = sl.sort_bins == columns;
+            } else {
+                // (SAME_TP_PROLOGUE=0, A/B measurements: the launches' start as rounds 2-5 made it)
+                HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 0, stream));
+                HIP_TRY(same::launch_init_state(tp.Pv, tp.Sv, 0, stream, C));
+                HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
+            }
+            if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (time-major), start-up: %s\n", columns,
+                                        tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
             HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
-            sort_bins_empty = sl.sort_bins == columns;
             const SampleT *xp = d_x + done * C;
             const uint32_t total_blocks = (uint32_t)(n / fbk);
             hipError_t e;
@@ -1478,6 +1492,35 @@ static int inv_launch_waiting(same_batch *rx, hipStream_t stream)
     if (rc) return rc;
     return inv_buffer_done(rx, stream);
 }
+// The input-lifetime contract (include/same_rx.h) in windowed mode.  A call's reads of the caller's buffer -- whole windows launched
+// in place, the pieces copied or cast into the waiting buffer, a channel-major call's copies into the staging buffers -- are all
+// queued on its stream, and a call shorter than a window launches nothing, so no harvest waits for them.  Each call therefore
+// records an event behind its last operation and, before it returns, waits for the one of the call before the previous one.
+// Successive calls' operations are kept in stream order whatever their streams (they share the staging and waiting buffers
+// too), so the latest event stands for every call before it: same_batch_sync and the host uploads wait for that one.
+static int inv_reads_begin(same_batch *rx, hipStream_t stream)
+{
+    same_batch::Windowed &iv = rx->inv;
+    if (iv.n_reads && iv.read_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, iv.ev_read[(iv.n_reads - 1) & 1], 0));
+    return SAME_OK;
+}
+static int inv_reads_end(same_batch *rx, hipStream_t stream)
+{
+    same_batch::Windowed &iv = rx->inv;
+    hipEvent_t &ev = iv.ev_read[iv.n_reads & 1];
+    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ev));           // call k - 2's reads: its buffer may be reused once this call returns
+    HIP_TRY(hipEventRecord(ev, stream));
+    iv.read_stream = stream;
+    ++iv.n_reads;
+    return SAME_OK;
+}
+static int inv_reads_wait(same_batch *rx)
+{
+    same_batch::Windowed &iv = rx->inv;
+    if (iv.n_reads) HIP_TRY(hipEventSynchronize(iv.ev_read[(iv.n_reads - 1) & 1]));
+    return SAME_OK;
+}
 template <typename SampleT>
 int process_time_major(same_batch *rx, const SampleT *d_x, size_t n_samples, hipStream_t stream)
 {
@@ -1634,6 +1677,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
         HIP_TRY(same::launch_init_state(tp.Pv, tp.Sv, 0, stream, C));
         HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
     }
+    if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (channel-major), start-up: %s\n", columns,
+                                tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
     HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
     pc.handover = sl.d_handover;
     pc.col_row0 = d_row0; pc.col_nominal = d_nom; pc.wg_blocks = d_wg; pc.col_perm = (sort_mode != 0 || pair_groups) ? d_perm : nullptr;
@@ -1694,6 +1739,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
 }
 
 template <typename SampleT>
+int process_device_on(same_batch *rx, const SampleT *d_x, size_t n_samples, uint32_t layout, hipStream_t stream);
+template <typename SampleT>
 int process_device_any(same_batch *rx, const SampleT *d_x, size_t n_samples, uint32_t layout, void *hip_stream)
 {
     if (!rx || (!d_x && n_samples)) return fail(SAME_EINVAL, "null argument");
@@ -1701,6 +1748,15 @@ int process_device_any(same_batch *rx, const SampleT *d_x, size_t n_samples, uin
     HIP_TRY(hipSetDevice(rx->device));
     // SAME_STREAM_OWN: the library's private stream; anything else (NULL included) is the caller's stream
     hipStream_t stream = hip_stream == SAME_STREAM_OWN ? rx->own_stream : (hipStream_t)hip_stream;
+    if (!rx->inv.on) return process_device_on(rx, d_x, n_samples, layout, stream);
+    int rc = inv_reads_begin(rx, stream);
+    if (rc == SAME_OK) rc = process_device_on(rx, d_x, n_samples, layout, stream);
+    const int rc_end = inv_reads_end(rx, stream);      // (also after a failed call: whatever it queued may read d_x)
+    return rc ? rc : rc_end;                            // the first error is the one reported; a second one is not
+}
+template <typename SampleT>
+int process_device_on(same_batch *rx, const SampleT *d_x, size_t n_samples, uint32_t layout, hipStream_t stream)
+{
     if (layout == SAME_LAYOUT_TIME_MAJOR) return process_time_major(rx, d_x, n_samples, stream);
     if (layout != SAME_LAYOUT_CHANNEL_MAJOR) return fail(SAME_EINVAL, "unknown layout %u", layout);
     if constexpr (sizeof(SampleT) == 4) {
@@ -1756,7 +1812,9 @@ int process_host_any(same_batch *rx, const SampleT *h_x, size_t n_samples, uint3
     for (size_t t0 = 0; t0 < n_samples && rc == SAME_OK; t0 += slab) {
         const size_t n = std::min(slab, n_samples - t0);
         hipError_t e;
-        // (the previous slab's launch was collected below, so the buffer is free again)
+        // (the previous slab's launch was collected below, so the buffer is free again -- unless a windowed batch only copied
+        // it into its waiting buffer, asynchronously: wait for that copy)
+        if (rx->inv.on && (rc = inv_reads_wait(rx)) != SAME_OK) break;
         if (layout == SAME_LAYOUT_TIME_MAJOR) {
             e = hipMemcpy(d_in, h_x + t0 * C, n * C * sizeof(SampleT), hipMemcpyHostToDevice);
         } else {
@@ -1923,6 +1981,7 @@ void same_batch_free(same_batch *rx)
     if (rx->d_tcold) (void)hipFree(rx->d_tcold);
     if (rx->inv.d_buf) (void)hipFree(rx->inv.d_buf);
     if (rx->inv.ev_buf) (void)hipEventDestroy(rx->inv.ev_buf);
+    for (hipEvent_t ev : rx->inv.ev_read) if (ev) (void)hipEventDestroy(ev);
     if (rx->tp.blob) (void)hipFree(rx->tp.blob);
     if (rx->tp.blob_fresh) (void)hipFree(rx->tp.blob_fresh);
     if (rx->tp.d_desc_in) (void)hipFree(rx->tp.d_desc_in);
@@ -2065,6 +2124,7 @@ int same_batch_sync(same_batch *rx)
     if (!rx) return fail(SAME_EINVAL, "null handle");
     HIP_TRY(hipSetDevice(rx->device));
     int rc = harvest(rx);
+    if (rc == SAME_OK && rx->inv.on) rc = inv_reads_wait(rx);      // (a call that only filled the waiting buffer made no launch)
     if (rc) return rc;
     if (rx->kernel_fault) return fail(SAME_EKERNEL, "a demodulation kernel's wavefronts lost step (internal hand-over timed out)");
     if (rx->overflowed) return fail(SAME_EOVERFLOW, "event/burst pool overflow");

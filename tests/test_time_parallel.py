@@ -561,9 +561,10 @@ def test_planning_on_the_plan_stream_and_on_a_callers_stream(sa, monkeypatch):
     assert np.array_equal(same["bytes"], got["bytes"])
 
 
-def test_prologue_kernel_on_a_time_major_call_equals_the_separate_launches(sa, monkeypatch):
+def test_prologue_kernel_on_a_time_major_call_equals_the_separate_launches(sa, monkeypatch, capfd):
     """A time-major time-parallel call (uniform cuts) starts with the same prologue kernel: the events of three streamed
-    calls must equal those of the launches that initialise their columns with init_state_kernel, call for call."""
+    calls must equal those of the launches that initialise their columns with init_state_kernel, call for call.  Which
+    start-up ran is read from the library's SAME_DEBUG line, so that the two runs cannot take the same path unnoticed."""
     rate, n_ch = 22050, 1024
     part = 22050 * 4
     part -= part % 1260
@@ -578,9 +579,15 @@ def test_prologue_kernel_on_a_time_major_call_equals_the_separate_launches(sa, m
         got = rx.poll_events_np()
         return got[np.lexsort((np.arange(len(got)), got["channel"]))]
 
+    monkeypatch.setenv("SAME_DEBUG", "1")
+    capfd.readouterr()
     a = run()
+    err = capfd.readouterr().err
+    assert err.count("start-up: prologue kernel") == 3 and "start-up: separate launches" not in err, err[-2000:]
     monkeypatch.setenv("SAME_TP_PROLOGUE", "0")
     b = run()
+    err = capfd.readouterr().err
+    assert err.count("start-up: separate launches") == 3 and "start-up: prologue kernel" not in err, err[-2000:]
     assert len(a) == len(b) and len(a) > 0 and (a["kind"] == 3).sum() > n_ch
     assert np.array_equal(a["kind"], b["kind"]) and np.array_equal(a["channel"], b["channel"])
     assert np.array_equal(a["sample_counter"], b["sample_counter"]) and np.array_equal(a["bytes"], b["bytes"])
