@@ -359,6 +359,53 @@ int same_batch_time_parallel_per_channel(const same_batch *rx);
 /* 1 when the last process call's transport layer ran on the device (SAME_BATCH_MESSAGES_ONLY, not time-parallel), else 0 */
 int same_batch_transport_on_device(const same_batch *rx);
 
+/* Alert audio per message (SAME_BATCH_MESSAGES_ONLY batches that are not time-parallel): what samedec hands its alert command
+ * (crates/samedec/src/app.rs:200-232).  The capture of a message is the channel's samples
+ *     x_c[som.sample_counter, next.sample_counter)
+ * in the channel's counters, where `next` is the channel's next queued message: an EndOfMessage, a forced one (135 s) or a new
+ * StartOfMessage, which opens its own capture.  same_batch_flush's zeros are never captured: a capture open at a flush ends at
+ * the flush position (SAME_AUDIO_END_FLUSH), and a StartOfMessage the flush itself yields gets an empty capture.
+ * same_batch_reset_channels ends the listed channels' open captures at the reset position (SAME_AUDIO_END_RESET, carrying the
+ * counter the capture had reached, before the reset); same_batch_reset closes every capture and clears the audio queue.  After
+ * a flush or a reset no capture is open on a channel until its next StartOfMessage; an EndOfMessage with none open does
+ * nothing.  int16 input is delivered converted exactly (int16(chunk) is the PCM).  Strict, SAME_BATCH_RELAXED (the span
+ * boundaries are the batch's own message counters), SAME_BATCH_CALL_INVARIANT (any list of calls gives the same chunks, bit for
+ * bit), both sample types, both layouts and same_batch_process_host* are covered.
+ * How.  The transport kernel lists, per launch, the rows of each channel that lie inside an open message and reserves their room
+ * in the launch's pool; a kernel behind it copies them out of the launch's input while the input is still the library's to read
+ * (the stream contract above is unchanged).  The launch's harvest -- the one that queues its messages -- copies the used part of
+ * the pool back and queues the chunks: once an EndOfMessage has been polled, all of that message's audio is queued.
+ * Chunks.  Queued per launch ordered by (channel, sample_counter); one channel's chunks are contiguous in sample_counter within
+ * a capture unless one is marked SAME_AUDIO_TRUNCATED.  SAME_AUDIO_FIRST marks a capture's first chunk (its sample_counter is
+ * the StartOfMessage's); SAME_AUDIO_END_* its last.  n_samples may be 0: a chunk that only carries an END_* flag, or the empty
+ * capture of a message at the end of a launch or of a flush.  A launch whose pool fills truncates the chunks that do not fit,
+ * marks them SAME_AUDIO_TRUNCATED, and the call returns SAME_EOVERFLOW as for an event log; later launches capture normally.
+ * same_batch_set_audio_capture(rx, samples_per_launch): before the batch's first sample or right after same_batch_reset
+ * (else SAME_EINVAL); SAME_EINVAL too for a batch without SAME_BATCH_MESSAGES_ONLY (its transport layer runs on the host, after
+ * the input is gone) and for a SAME_BATCH_TIME_PARALLEL batch.  It allocates the pools now, so that running out of memory fails
+ * here (SAME_ENOMEM); 0 turns capture off.  Memory: two slots x samples_per_launch x 4 bytes on the device, a list of 32-byte
+ * span records per slot (n_channels + the message log's capacity), 16 bytes per channel, and pinned host staging that grows to
+ * the largest launch's captured samples.  A launch is at most one process call (at most 2^22 samples per channel): one that
+ * keeps a quarter of 32 768 channels x 2 s inside messages needs 361 M samples.  Cost: DESIGN.md 4.9.
+ * same_batch_peek_audio / same_batch_drop_audio: as same_batch_peek_events / same_batch_drop_events -- *chunks points at *n
+ * queued chunks, and every `samples` pointer stays valid as long as a peek view of same_batch_peek_events would. */
+enum {
+    SAME_AUDIO_FIRST = 1,
+    SAME_AUDIO_END_MESSAGE = 2,
+    SAME_AUDIO_END_FLUSH = 4,
+    SAME_AUDIO_END_RESET = 8,
+    SAME_AUDIO_TRUNCATED = 16
+};
+typedef struct same_audio_chunk {
+    uint32_t channel, flags;
+    uint64_t sample_counter;     /* the channel's counter (rebased like events) of samples[0] */
+    uint64_t n_samples;
+    const float *samples;        /* handle-owned */
+} same_audio_chunk;
+int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch);
+int same_batch_peek_audio(same_batch *rx, const same_audio_chunk **chunks, size_t *n);
+int same_batch_drop_audio(same_batch *rx, size_t n);
+
 /* soft-symbol trace (SAME_BATCH_TRACE_SYMBOLS): SymbolEstimate stream of one channel
  * (rx/symsync.rs:52-71) with the input sample counter of each TED instant */
 typedef struct same_symbol_trace {

@@ -9,4 +9,5 @@ from .receiver import (  # noqa: F401
     LINK_BURST, LINK_NO_CARRIER, LINK_READING, LINK_SEARCHING,
     TRANSPORT_ASSEMBLING, TRANSPORT_IDLE, TRANSPORT_MSG_END, TRANSPORT_MSG_ERR, TRANSPORT_MSG_START,
     decode_recordings, load_library, synth_afsk, synth_payload,
+    AUDIO_END, AUDIO_END_FLUSH, AUDIO_END_MESSAGE, AUDIO_END_RESET, AUDIO_FIRST, AUDIO_TRUNCATED, AudioChunk, AudioJoiner,
 )

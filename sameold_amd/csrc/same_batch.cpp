@@ -106,6 +106,12 @@ struct PodQueue {                    // a plain growable array of PODs (no zero-
     }
 };
 using EventQueue = PodQueue<QEvent>;
+// a queued chunk of alert audio (same_batch_set_audio_capture): its samples are [at, at + n) of the sample arena (absolute index)
+struct AudioChunk {
+    uint32_t channel, flags;
+    uint64_t sample_counter, n;
+    uint64_t at;
+};
 using ByteArena = PodQueue<uint8_t>;     // payload bytes: element number = absolute offset
 // SAME_HOST_PROF (measurement builds: SAME_EXTRA_DEFS=SAME_HOST_PROF=1): time-stamp-counter totals of the replay's parts,
 // printed by same_debug_harvest_replay (one thread); nothing in the product build
@@ -256,6 +262,14 @@ struct same_batch {
         same::DevMessage *h_near = nullptr, *h_near_dev = nullptr; uint32_t near_cap = 0;
         same::DevMessage *d_msgs = nullptr; uint32_t msg_cap = 0;
         void *h_msgs = nullptr; size_t h_msgs_bytes = 0;
+        // same_batch_set_audio_capture: the launch's span list and sample pool (same_capture_dev.h, same_capture.hip), their
+        // cursors (device; published to the host-mapped copy by the capture kernel's epilogue) and pinned landing buffers
+        bool captured = false;           // this launch ran the capture kernel
+        same::cap::Span *d_spans = nullptr; uint32_t span_cap = 0;
+        float *d_pool = nullptr;
+        same::cap::Cursors *d_cap_cur = nullptr, *h_cap_cur = nullptr, *h_cap_cur_dev = nullptr;
+        void *h_spans = nullptr; size_t h_spans_bytes = 0;
+        void *h_pool = nullptr; size_t h_pool_bytes = 0;
     } slot[2];
     // time-parallel mode (SAME_BATCH_TIME_PARALLEL)
     struct TimePar {
@@ -360,6 +374,17 @@ struct same_batch {
     // per-channel resets (same_batch_reset_channels): where each half of a reset is due, the channels' counter bases
     same::ResetLedger resets;
     std::vector<uint32_t> reset_list, reset_now, reset_cols;       // scratch: the entry point's, the reset kernel's list
+    // alert audio per message (same_batch_set_audio_capture)
+    struct Audio {
+        size_t per_launch = 0;                   // pool samples per slot; 0: capture is off
+        same::cap::Rec *d_rec = nullptr;         // per channel: the device's capture record
+        std::vector<uint8_t> open;               // per channel: a capture is open as far as the queued chunks go (END_RESET chunks)
+        uint64_t flush_at = UINT64_MAX;          // batch counter where the running same_batch_flush began
+        PodQueue<AudioChunk> queue;              // chunks not yet dropped: [head, size)
+        size_t head = 0;
+        PodQueue<float> samples;                 // their samples (element number = absolute index)
+        std::vector<same_audio_chunk> view;      // same_batch_peek_audio
+    } audio;
 };
 
 static void release_stale_view(same_batch *rx);
@@ -502,6 +527,17 @@ int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::
             HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_near_dev, sl.h_near, 0));
             sl.near_cap = want;
         }
+        if (rx->audio.per_launch) {
+            // a message ends at most one span, a channel's tail or flush adds one: spans past this are lost only when the
+            // message log overflows too
+            const size_t scap = std::min<size_t>(n_ch + (size_t)sl.near_cap + sl.msg_cap, 0x7fffffffu / sizeof(same::cap::Span));
+            if (scap > sl.span_cap) {
+                if (sl.d_spans) HIP_TRY(hipFree(sl.d_spans));
+                sl.d_spans = nullptr; sl.span_cap = 0;
+                HIP_TRY(hipMalloc((void **)&sl.d_spans, scap * sizeof(same::cap::Span)));
+                sl.span_cap = (uint32_t)scap;
+            }
+        }
     }
     {
         const size_t need = 2 * n_ch + 1 + same::event_sort_extra_words((uint32_t)n_ch), need_h = n_ch + 1;
@@ -599,7 +635,8 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
     std::memcpy(sl.h_reset, cols.data(), (size_t)n * sizeof(uint32_t));
     hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset_dev, n, stream);
     // (SAME_BATCH_MESSAGES_ONLY: the transport layer lives on the device, and is reset there at the same position)
-    if (e == hipSuccess && rx->dev_transport) e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, sl.h_reset_dev, n, 0, stream);
+    if (e == hipSuccess && rx->dev_transport)
+        e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, sl.h_reset_dev, n, 0, stream, rx->audio.d_rec);
     if (e != hipSuccess) return fail(SAME_EHIP, "channel reset launch failed: %s", hipGetErrorString(e));
     return SAME_OK;
 }
@@ -931,6 +968,93 @@ hipError_t grow_pinned(void **p, size_t *have, size_t need)
     return e;
 }
 
+// Before chunks are appended to the audio queue: reclaim the dropped prefix once it is at least as large as what is still queued
+// (the queue and the sample arena move: a view of same_batch_peek_audio is stale by then anyway)
+AudioChunk *audio_grow(same_batch *rx, size_t n_chunks, size_t n_samples, float **samples_at, uint64_t *at)
+{
+    same_batch::Audio &A = rx->audio;
+    if (A.head && A.head >= A.queue.size() - A.head) {
+        A.head = A.queue.compact(A.head);
+        const uint64_t keep_from = A.queue.size() ? A.queue.data()[0].at : A.samples.base + A.samples.size();
+        A.samples.compact((size_t)(keep_from - A.samples.base));
+    }
+    AudioChunk *dst = A.queue.grow(n_chunks);
+    if (n_chunks && !dst) return nullptr;
+    float *sdst = A.samples.grow(n_samples);
+    if (n_samples && !sdst) { A.queue.n -= n_chunks; return nullptr; }
+    *samples_at = sdst;
+    *at = A.samples.base + (A.samples.size() - n_samples);
+    return dst;
+}
+
+// The channels' open captures end at a reset (same_batch_reset_channels) at batch position `pos`: an empty END_RESET chunk at the
+// counter the capture had reached.  Called once every chunk before `pos` is queued, before the channels' counter bases move.
+int audio_end_reset(same_batch *rx, const std::vector<uint32_t> &chans, uint64_t pos)
+{
+    same_batch::Audio &A = rx->audio;
+    if (!A.per_launch) return SAME_OK;
+    size_t n = 0;
+    for (uint32_t c : chans) n += A.open[c];
+    if (!n) return SAME_OK;
+    float *sdst = nullptr;
+    uint64_t at = 0;
+    AudioChunk *dst = audio_grow(rx, n, 0, &sdst, &at);
+    if (!dst) return fail(SAME_ENOMEM, "audio queue");
+    for (uint32_t c : chans) {
+        if (!A.open[c]) continue;
+        *dst++ = AudioChunk{c, SAME_AUDIO_END_RESET, rx->resets.rebase(c, pos), 0, at};
+        A.open[c] = 0;
+    }
+    return SAME_OK;
+}
+
+// The audio of a launch that captured (same_capture.hip): the spans and the used part of the pool come back on the copy stream
+// (nothing when no capture was open), then go to the queue by (channel, emission order) -- a lane lists its spans in counter order.
+int harvest_audio(same_batch *rx, same_batch::Slot &sl)
+{
+    sl.captured = false;
+    same_batch::Audio &A = rx->audio;
+    const same::cap::Cursors cur = *sl.h_cap_cur;
+    if (cur.overflow) rx->overflowed = true;
+    const uint32_t n_spans = std::min(cur.n_spans, sl.span_cap);
+    if (!n_spans) return SAME_OK;
+    const size_t used = (size_t)std::min<unsigned long long>(cur.pool_used, (unsigned long long)A.per_launch);
+    HIP_TRY(grow_pinned(&sl.h_spans, &sl.h_spans_bytes, (size_t)n_spans * sizeof(same::cap::Span)));
+    HIP_TRY(hipMemcpyAsync(sl.h_spans, sl.d_spans, (size_t)n_spans * sizeof(same::cap::Span), hipMemcpyDeviceToHost, rx->copy_stream));
+    if (used) {
+        HIP_TRY(grow_pinned(&sl.h_pool, &sl.h_pool_bytes, used * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(sl.h_pool, sl.d_pool, used * sizeof(float), hipMemcpyDeviceToHost, rx->copy_stream));
+    }
+    HIP_TRY(hipStreamSynchronize(rx->copy_stream));
+    const same::cap::Span *sp = static_cast<const same::cap::Span *>(sl.h_spans);
+    const float *pool = static_cast<const float *>(sl.h_pool);
+    std::vector<uint32_t> order(n_spans);
+    size_t n_samples = 0;
+    for (uint32_t i = 0; i < n_spans; ++i) {
+        order[i] = i;
+        if (sp[i].n && sp[i].off + sp[i].n <= used) n_samples += sp[i].n;
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sp[a].channel != sp[b].channel ? sp[a].channel < sp[b].channel : a < b; });
+    float *sdst = nullptr;
+    uint64_t at = 0;
+    AudioChunk *dst = audio_grow(rx, n_spans, n_samples, &sdst, &at);
+    if (!dst) return fail(SAME_ENOMEM, "audio queue");
+    for (uint32_t k = 0; k < n_spans; ++k) {
+        const same::cap::Span &s = sp[order[k]];
+        const uint32_t n = s.n && s.off + s.n <= used ? s.n : 0;
+        uint32_t flags = s.flags;
+        if (n < s.n) flags |= SAME_AUDIO_TRUNCATED;
+        dst[k] = AudioChunk{s.channel, flags, rx->resets.rebase(s.channel, s.counter), n, at};
+        if (n) { std::memcpy(sdst, pool + s.off, (size_t)n * sizeof(float)); sdst += n; at += n; }
+        if (flags & SAME_AUDIO_FIRST) A.open[s.channel] = 1;
+        if (flags & (SAME_AUDIO_END_MESSAGE | SAME_AUDIO_END_FLUSH | SAME_AUDIO_END_RESET)) A.open[s.channel] = 0;
+    }
+    if (rx->debug)
+        std::fprintf(stderr, "[same] audio: %u chunks, %zu samples (pool %zu of %zu)%s\n", n_spans, n_samples, used, A.per_launch,
+                     cur.overflow ? ", truncated" : "");
+    return SAME_OK;
+}
+
 // The harvest of a launch that ran the transport layer on the device (SAME_BATCH_MESSAGES_ONLY): its message log is all that
 // comes back -- no event log, no burst pool, no replay.  The log's order across lanes is that of their atomics; the queue
 // takes it by channel and, per channel, in the order the lane logged it (= iter_events() filtered to messages).
@@ -977,8 +1101,14 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
         }
         dst[k] = q;
     }
+    if (sl.captured) {
+        const int arc = harvest_audio(rx, sl);
+        if (arc) return arc;
+    }
     // the harvest has reached the resets asked for behind this launch: their host half (the counter bases) is due
     const int si = (int)(&sl - rx->slot);
+    // (the open captures of the channels end there, in their counters before the reset)
+    if (const int arc = audio_end_reset(rx, rx->resets.slot[si & 1].channels, rx->resets.rec_pos(si))) return arc;
     for (uint32_t c : rx->resets.host_due(si)) reset_channel_host(rx, c, rx->resets.rec_pos(si));
     rx->resets.done_host(si);
     if (rx->debug) {
@@ -1414,7 +1544,30 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             T.hot = rx->d_thot; T.cold = rx->d_tcold; T.wake_sample = rx->S.wake_sample;
             T.near = sl.h_near_dev; T.near_cap = sl.near_cap;
             T.log = sl.d_msgs; T.log_cap = sl.msg_cap; T.log_cursor = sl.d_counters + 3; T.overflow = sl.d_counters + 2;
+            // same_batch_set_audio_capture: the lanes list the spans of open messages, the capture kernel copies them out of the
+            // input behind it -- before the launch's done event, which every later reuse of the input waits for
+            sl.captured = rx->audio.per_launch != 0;
+            if (sl.captured) {
+                same::cap::Launch &K = T.cap;
+                const uint64_t fa = rx->audio.flush_at;
+                K.start = rx->counter; K.n_rows = (uint32_t)n;
+                K.flush_row = fa >= rx->counter + n ? same::cap::kNoFlush : (uint32_t)(fa > rx->counter ? fa - rx->counter : 0);
+                K.rec = rx->audio.d_rec; K.spans = sl.d_spans; K.span_cap = sl.span_cap;
+                K.n_spans = &sl.d_cap_cur->n_spans; K.pool_used = &sl.d_cap_cur->pool_used; K.pool_cap = rx->audio.per_launch;
+                K.overflow = &sl.d_cap_cur->overflow;
+            }
             HIP_TRY(same::launch_transport(T, stream));
+            if (sl.captured) {
+                const SampleT *xc = d_x + done * rx->P.n_channels;
+                hipError_t e;
+                if constexpr (sizeof(SampleT) == 4)
+                    e = same::launch_capture(sl.d_spans, sl.d_cap_cur, sl.span_cap, sl.d_pool, rx->audio.per_launch, (const float *)xc,
+                                             rx->P.n_channels, (uint32_t)n, sl.h_cap_cur_dev, stream);
+                else
+                    e = same::launch_capture_i16(sl.d_spans, sl.d_cap_cur, sl.span_cap, sl.d_pool, rx->audio.per_launch, (const int16_t *)xc,
+                                                 rx->P.n_channels, (uint32_t)n, sl.h_cap_cur_dev, stream);
+                if (e != hipSuccess) return fail(SAME_EHIP, "capture kernel launch failed: %s", hipGetErrorString(e));
+            }
         }
         HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 1, stream));
         HIP_TRY(hipEventRecord(sl.ev_done, stream));
@@ -1976,7 +2129,14 @@ void same_batch_free(same_batch *rx)
         if (sl.d_msgs) (void)hipFree(sl.d_msgs);
         if (sl.h_near) (void)hipHostFree(sl.h_near);
         if (sl.h_msgs) (void)hipHostFree(sl.h_msgs);
+        if (sl.d_spans) (void)hipFree(sl.d_spans);
+        if (sl.d_pool) (void)hipFree(sl.d_pool);
+        if (sl.d_cap_cur) (void)hipFree(sl.d_cap_cur);
+        if (sl.h_cap_cur) (void)hipHostFree(sl.h_cap_cur);
+        if (sl.h_spans) (void)hipHostFree(sl.h_spans);
+        if (sl.h_pool) (void)hipHostFree(sl.h_pool);
     }
+    if (rx->audio.d_rec) (void)hipFree(rx->audio.d_rec);
     if (rx->d_thot) (void)hipFree(rx->d_thot);
     if (rx->d_tcold) (void)hipFree(rx->d_tcold);
     if (rx->inv.d_buf) (void)hipFree(rx->inv.d_buf);
@@ -2009,7 +2169,8 @@ int same_batch_reset(same_batch *rx)
     int rc = harvest(rx);
     if (rc) return rc;
     hipError_t e = same::launch_init_state(rx->P, rx->S, 1, rx->own_stream);
-    if (e == hipSuccess && rx->dev_transport) e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, nullptr, 0, 0, rx->own_stream);
+    if (e == hipSuccess && rx->dev_transport)
+        e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, nullptr, 0, 0, rx->own_stream, rx->audio.d_rec);
     if (e != hipSuccess) return fail(SAME_EHIP, "reset launch failed: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(rx->own_stream));
     rx->counter = 0;
@@ -2026,6 +2187,11 @@ int same_batch_reset(same_batch *rx)
     rx->resets.clear();                      // (per-channel resets still due are covered: every column was re-initialised)
     rx->overflowed = false;
     rx->kernel_fault = false;
+    // the audio queue goes with the event queue, and every capture is closed (the reset kernel closed the device's records)
+    rx->audio.queue.clear(); rx->audio.head = 0; rx->audio.samples.clear();
+    std::vector<same_audio_chunk>().swap(rx->audio.view);
+    std::fill(rx->audio.open.begin(), rx->audio.open.end(), 0);
+    rx->audio.flush_at = UINT64_MAX;
     return SAME_OK;
 }
 
@@ -2048,6 +2214,11 @@ int same_batch_reset_channels(same_batch *rx, const uint32_t *channels, size_t n
     int newest = -1;
     for (int s = 0; s < 2; ++s)
         if (rx->slot[s].in_flight && (newest < 0 || rx->slot[s].seq > rx->slot[newest].seq)) newest = s;
+    if (newest < 0) {
+        // every launch before the position is harvested: the open captures end here (in the counters before the reset)
+        const int arc = audio_end_reset(rx, rx->reset_list, rx->counter);
+        if (arc) return arc;
+    }
     rx->resets.request(rx->reset_list, rx->counter, newest, rx->reset_now);
     for (uint32_t c : rx->reset_now) reset_channel_host(rx, c, rx->counter);
     return SAME_OK;
@@ -2086,6 +2257,7 @@ int same_batch_flush(same_batch *rx)
         HIP_TRY(hipMemset(rx->d_zero, 0, rx->zero_bytes));       // once per growth: the kernels only read it
     }
     int rc = SAME_OK;
+    rx->audio.flush_at = rx->counter + rx->inv.fill;      // (the zeros are never captured: a launch's rows from here on are clipped)
     for (size_t t0 = 0; t0 < n && rc == SAME_OK; t0 += slab) {
         rc = process_device_any<float>(rx, (const float *)rx->d_zero, std::min(slab, n - t0), SAME_LAYOUT_TIME_MAJOR, SAME_STREAM_OWN);
         if (rc == SAME_OK) rc = harvest(rx);
@@ -2095,6 +2267,7 @@ int same_batch_flush(same_batch *rx)
         rc = inv_launch_waiting(rx, rx->own_stream);
         if (rc == SAME_OK) rc = harvest(rx);
     }
+    rx->audio.flush_at = UINT64_MAX;
     return rc;
 }
 
@@ -2226,6 +2399,76 @@ int same_batch_drop_events(same_batch *rx, size_t n)
     if (n > rx->queue.size() - rx->queue_head) return fail(SAME_EINVAL, "more events than are queued");
     rx->queue_head += n;
     if (rx->queue_head == rx->queue.size()) queue_emptied(rx, /*view_may_be_read=*/true);
+    return SAME_OK;
+}
+
+int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
+{
+    if (!rx) return fail(SAME_EINVAL, "null handle");
+    if (!rx->messages_only) return fail(SAME_EINVAL, "audio capture needs SAME_BATCH_MESSAGES_ONLY (the transport layer on the device)");
+    if (rx->tp.enabled) return fail(SAME_EINVAL, "audio capture is not available in SAME_BATCH_TIME_PARALLEL batches");
+    if (rx->counter || rx->inv.fill) return fail(SAME_EINVAL, "audio capture is set before the first sample (or right behind a reset)");
+    HIP_TRY(hipSetDevice(rx->device));
+    int rc = harvest(rx);
+    if (rc) return rc;
+    same_batch::Audio &A = rx->audio;
+    auto release = [&]() {
+        for (same_batch::Slot &sl : rx->slot) {
+            if (sl.d_pool) (void)hipFree(sl.d_pool);
+            if (sl.d_spans) (void)hipFree(sl.d_spans);
+            sl.d_pool = nullptr; sl.d_spans = nullptr; sl.span_cap = 0;
+        }
+        if (A.d_rec) (void)hipFree(A.d_rec);
+        A.d_rec = nullptr;
+        A.per_launch = 0;
+        A.open.clear();
+    };
+    release();
+    if (!samples_per_launch) return SAME_OK;
+    if (samples_per_launch > ((size_t)1 << 40)) return fail(SAME_EINVAL, "%zu samples per launch", samples_per_launch);
+    auto oom = [&](const char *what) {
+        (void)hipGetLastError();
+        release();
+        return fail(SAME_ENOMEM, "audio capture: %s (%zu samples per launch)", what, samples_per_launch);
+    };
+    for (same_batch::Slot &sl : rx->slot) {
+        if (hipMalloc((void **)&sl.d_pool, samples_per_launch * sizeof(float)) != hipSuccess) return oom("sample pool");
+        if (!sl.d_cap_cur) {
+            if (hipMalloc((void **)&sl.d_cap_cur, sizeof(same::cap::Cursors)) != hipSuccess) return oom("cursors");
+            HIP_TRY(hipMemset(sl.d_cap_cur, 0, sizeof(same::cap::Cursors)));
+            if (hipHostMalloc((void **)&sl.h_cap_cur, sizeof(same::cap::Cursors), hipHostMallocMapped) != hipSuccess) return oom("cursors");
+            HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_cap_cur_dev, sl.h_cap_cur, 0));
+        }
+    }
+    if (hipMalloc((void **)&A.d_rec, (size_t)rx->P.n_channels * sizeof(same::cap::Rec)) != hipSuccess) return oom("capture records");
+    HIP_TRY(hipMemset(A.d_rec, 0, (size_t)rx->P.n_channels * sizeof(same::cap::Rec)));
+    A.open.assign(rx->P.n_channels, 0);
+    A.per_launch = samples_per_launch;
+    return SAME_OK;
+}
+
+int same_batch_peek_audio(same_batch *rx, const same_audio_chunk **chunks, size_t *n)
+{
+    if (!rx || !chunks || !n) return fail(SAME_EINVAL, "null argument");
+    same_batch::Audio &A = rx->audio;
+    const size_t avail = A.queue.size() - A.head;
+    try { A.view.resize(avail); } catch (...) { return fail(SAME_ENOMEM, "audio view"); }
+    const AudioChunk *q = A.queue.data() + A.head;
+    for (size_t i = 0; i < avail; ++i) {
+        same_audio_chunk &o = A.view[i];
+        o.channel = q[i].channel; o.flags = q[i].flags; o.sample_counter = q[i].sample_counter; o.n_samples = q[i].n;
+        o.samples = A.samples.data() + (size_t)(q[i].at - A.samples.base);
+    }
+    *n = avail;
+    *chunks = avail ? A.view.data() : nullptr;
+    return SAME_OK;
+}
+
+int same_batch_drop_audio(same_batch *rx, size_t n)
+{
+    if (!rx) return fail(SAME_EINVAL, "null argument");
+    if (n > rx->audio.queue.size() - rx->audio.head) return fail(SAME_EINVAL, "more chunks than are queued");
+    rx->audio.head += n;       // (the memory is reclaimed by the next harvest that queues chunks: a view may still be read)
     return SAME_OK;
 }
 

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "same_capture_dev.h"
 #include "same_device.h"
 
 namespace same {
@@ -120,14 +121,23 @@ struct TransportLaunch {
     DevMessage *near; uint32_t near_cap;
     DevMessage *log; uint32_t log_cap;
     uint32_t *log_cursor, *overflow;
+    cap::Launch cap;               // same_batch_set_audio_capture (cap.rec == nullptr: off, the kernel does nothing more)
 };
 size_t transport_hot_bytes();
 size_t transport_cold_bytes();
 hipError_t launch_transport(const TransportLaunch &T, hipStream_t stream);
 // reset() of the transport layer of the columns cols[0 .. n) (device-readable), or of every channel (cols == nullptr); fresh: the
-// records were never written (a new batch)
+// records were never written (a new batch); capture_rec: the channels' capture records (cap::Rec), closed too, or nullptr
 hipError_t launch_transport_reset(void *hot, void *cold, uint32_t n_channels, const uint32_t *cols, uint32_t n, int fresh,
-                                  hipStream_t stream);
+                                  hipStream_t stream, void *capture_rec = nullptr);
+// The capture kernel (same_capture.hip, same_batch_set_audio_capture): behind launch_transport, on the launch's stream, it copies
+// the spans the transport kernel listed (their number: *n_spans, read on the device) out of the launch's input x (time-major, row
+// pitch n_channels, n_rows rows) into the pool.  A fixed grid, whatever the number of spans.
+// Then its epilogue copies the launch's cursors to `host` (host-mapped) and zeroes them.
+hipError_t launch_capture(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
+                          const float *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream);
+hipError_t launch_capture_i16(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
+                              const int16_t *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream);
 
 // synthetic workload (same_synth.hip)
 struct SynthParams {

@@ -9,6 +9,7 @@
 
 #include "same_device.h"
 #include "same_launch.h"
+#include "same_capture_dev.h"
 #include "same_transport_dev.h"
 
 namespace same {
@@ -36,6 +37,9 @@ __global__ __launch_bounds__(64) void transport_kernel(TransportLaunch T)
     dt::Msg msg;
     dt::Event out;
     uint32_t seq = 0;
+    // same_batch_set_audio_capture: the spans of this launch's rows that belong to an open message (same_capture_dev.h)
+    const bool capture = T.cap.rec != nullptr;
+    cap::Walker w(T.cap, capture ? c : 0u);
     for (uint32_t i = b; i < e; ++i) {
         const DevEvent d = ev[i];
         const uint8_t *bytes = nullptr;
@@ -46,6 +50,7 @@ __global__ __launch_bounds__(64) void transport_kernel(TransportLaunch T)
         }
         if (!tr.on_link_event(d.kind, d.sample_counter, d.symbol_count, bytes, len, T.input_rate, msg, &out)) continue;
         if (out.kind != SAME_TRANSPORT_MSG_START && out.kind != SAME_TRANSPORT_MSG_END) continue;
+        if (capture) w.on_message(out.kind, out.sample_counter);
         const uint32_t k = atomicAdd(T.log_cursor, 1u);
         if (k >= T.near_cap && k - T.near_cap >= T.log_cap) { atomicOr(T.overflow, kMessageLogOverflow); continue; }
         DevMessage &m = k < T.near_cap ? T.near[k] : T.log[k - T.near_cap];
@@ -57,11 +62,13 @@ __global__ __launch_bounds__(64) void transport_kernel(TransportLaunch T)
     // (State::wake_sample); a changed instant is armed for the next launch, which is ordered behind this kernel
     if (tr.force_eom_dirty()) T.wake_sample[c] = tr.force_eom_at();
     hot[c] = h;
+    if (capture) w.finish();
 }
 
 // SameReceiver::reset() of the transport layer (receiver.rs:195-196): the listed channels, or all of them (cols == nullptr)
+// (cap: the channels' capture records, or nullptr: an open capture ends at the reset -- the host queues its END_RESET chunk)
 __global__ __launch_bounds__(64) void transport_reset_kernel(dt::Hot *hot, dt::Cold *cold, uint32_t n_channels, const uint32_t *cols,
-                                                             uint32_t n, int fresh)
+                                                             uint32_t n, int fresh, cap::Rec *rec)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (cols ? n : n_channels)) return;
@@ -72,6 +79,7 @@ __global__ __launch_bounds__(64) void transport_reset_kernel(dt::Hot *hot, dt::C
     dt::Transport tr{h, cold[c]};
     tr.reset();
     hot[c] = h;
+    if (rec) rec[c] = cap::Rec{0, 0, 0};
 }
 
 }  // namespace
@@ -87,12 +95,12 @@ hipError_t launch_transport(const TransportLaunch &T, hipStream_t stream)
 }
 
 hipError_t launch_transport_reset(void *hot, void *cold, uint32_t n_channels, const uint32_t *cols, uint32_t n, int fresh,
-                                  hipStream_t stream)
+                                  hipStream_t stream, void *capture_rec)
 {
     const uint32_t count = cols ? n : n_channels;
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(transport_reset_kernel, dim3((count + 63u) / 64u), dim3(64), 0, stream, static_cast<dt::Hot *>(hot),
-                       static_cast<dt::Cold *>(cold), n_channels, cols, n, fresh);
+                       static_cast<dt::Cold *>(cold), n_channels, cols, n, fresh, static_cast<cap::Rec *>(capture_rec));
     return hipGetLastError();
 }
 

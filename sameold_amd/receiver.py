@@ -31,6 +31,9 @@ BATCH_MESSAGES_ONLY = 64            # SAME_BATCH_MESSAGES_ONLY: only MSG_START /
 TP_EVENT_TOLERANCE_SYMBOLS = 2      # SAME_TP_EVENT_TOLERANCE_SYMBOLS
 STREAM_OWN = (1 << 64) - 1          # SAME_STREAM_OWN: (void *)-1, the library's own stream
 EVENT_MAX_BYTES = 288
+# same_audio_chunk flags (same_batch_set_audio_capture)
+AUDIO_FIRST, AUDIO_END_MESSAGE, AUDIO_END_FLUSH, AUDIO_END_RESET, AUDIO_TRUNCATED = 1, 2, 4, 8, 16
+AUDIO_END = AUDIO_END_MESSAGE | AUDIO_END_FLUSH | AUDIO_END_RESET
 
 ERRORS = {-1: "EINVAL", -2: "EDCLEN", -3: "EAGCLIMITS", -4: "EEQORDER", -5: "ENODEVICE",
           -6: "EHIP", -7: "EOVERFLOW", -8: "ENOMEM", -9: "ERATE", -10: "EKERNEL"}
@@ -82,6 +85,12 @@ EVENT_DTYPE = np.dtype([("kind", "<u4"), ("channel", "<u4"), ("sample_counter", 
                         ("len", "<u4"), ("aux", "<u4"), ("aux2", "<u4"), ("reserved", "<u4"),
                         ("bytes", "u1", (EVENT_MAX_BYTES,))])
 assert EVENT_DTYPE.itemsize == C.sizeof(Event)
+
+
+class AudioChunk(C.Structure):
+    """`same_audio_chunk` (include/same_rx.h)"""
+    _fields_ = [("channel", C.c_uint32), ("flags", C.c_uint32), ("sample_counter", C.c_uint64), ("n_samples", C.c_uint64),
+                ("samples", C.POINTER(C.c_float))]
 
 
 class SymbolTrace(C.Structure):
@@ -178,6 +187,9 @@ def load_library() -> C.CDLL:
     sig("same_batch_time_parallel_chunks", u32, vp)
     sig("same_batch_time_parallel_per_channel", C.c_int, vp)
     sig("same_batch_transport_on_device", C.c_int, vp)
+    sig("same_batch_set_audio_capture", C.c_int, vp, C.c_size_t)
+    sig("same_batch_peek_audio", C.c_int, vp, P(P(AudioChunk)), P(C.c_size_t))
+    sig("same_batch_drop_audio", C.c_int, vp, C.c_size_t)
     sig("same_rx_source_hash", C.c_char_p)
     sig("same_batch_process_device_i16", C.c_int, vp, vp, C.c_size_t, u32, vp)
     sig("same_batch_process_host", C.c_int, vp, vp, C.c_size_t, u32)
@@ -405,6 +417,27 @@ class SameBatchReceiver:
     def time_parallel_per_channel(self) -> bool:
         """Whether that call's chunk boundaries were chosen per channel (channel-major input, see same_rx.h)."""
         return bool(self._L.same_batch_time_parallel_per_channel(self._h))
+
+    def set_audio_capture(self, samples_per_launch: int) -> None:
+        """Capture the alert audio of every message (same_batch_set_audio_capture): messages_only batches that are not
+        time-parallel, before the first sample or right after reset().  `samples_per_launch`: the pool of one launch (two are
+        allocated on the device now); 0 turns capture off."""
+        _check(self._L.same_batch_set_audio_capture(self._h, int(samples_per_launch)))
+
+    def poll_audio(self) -> list:
+        """The queued audio chunks as (channel, sample_counter, flags, numpy float32 array) tuples, which are then dropped.
+        Non-blocking, like poll_events: a launch contributes its chunks when it is harvested."""
+        ptr, n = C.POINTER(AudioChunk)(), C.c_size_t()
+        _check(self._L.same_batch_peek_audio(self._h, C.byref(ptr), C.byref(n)))
+        out = []
+        for i in range(n.value):
+            ch = ptr[i]
+            k = int(ch.n_samples)
+            a = np.ctypeslib.as_array(ch.samples, shape=(k,)).copy() if k else np.zeros(0, np.float32)
+            out.append((int(ch.channel), int(ch.sample_counter), int(ch.flags), a))
+        if n.value:
+            _check(self._L.same_batch_drop_audio(self._h, n.value))
+        return out
 
     def process_device_ptr(self, ptr: int, n_samples: int, layout: int = LAYOUT_TIME_MAJOR,
                            stream: Optional[int] = None, i16: bool = False):
@@ -665,6 +698,41 @@ def decode_recordings(recordings: Sequence, input_rate: int, n_channels: int,
                 owner[c] = nxt if nxt < len(tapes) else -1
                 nxt += nxt < len(tapes)
     return out
+
+
+class AudioJoiner:
+    """Joins one batch's audio chunks (SameBatchReceiver.poll_audio) into one array per message, once its END_* chunk has
+    arrived.  feed() returns the captures completed by the chunks given, in arrival order, as dicts: channel, sample_counter
+    (of the first sample: the StartOfMessage's), end (SAME_AUDIO_END_* flag), truncated (a chunk was marked TRUNCATED),
+    samples (numpy float32).  `open` holds the captures still running, by channel."""
+
+    def __init__(self):
+        self.open = {}
+
+    def feed(self, chunks) -> list:
+        done = []
+        for channel, counter, flags, samples in chunks:
+            cur = self.open.get(channel)
+            if flags & AUDIO_FIRST:
+                if cur is not None:
+                    raise ValueError(f"channel {channel}: a capture began at {counter} while the one of {cur['sample_counter']} was open")
+                cur = self.open[channel] = {"channel": channel, "sample_counter": counter, "end": 0, "truncated": False,
+                                            "parts": [], "next": counter}
+            elif cur is None:
+                raise ValueError(f"channel {channel}: a chunk at {counter} outside any capture")
+            if counter != cur["next"] and not cur["truncated"]:
+                raise ValueError(f"channel {channel}: chunk at {counter}, the capture had reached {cur['next']}")
+            cur["truncated"] |= bool(flags & AUDIO_TRUNCATED)
+            cur["parts"].append(samples)
+            cur["next"] = counter + len(samples)
+            if flags & AUDIO_END:
+                del self.open[channel]
+                parts = cur.pop("parts")
+                cur.pop("next")
+                cur["end"] = flags & AUDIO_END
+                cur["samples"] = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+                done.append(cur)
+        return done
 
 
 def synth_afsk(n_channels: int, n_samples: int, input_rate: int = 22050, seed: int = 1,
