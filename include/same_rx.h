@@ -130,7 +130,8 @@ typedef struct same_rx_event {
  * `n_channels` independent `SameReceiver`s built from one builder
  * (`SameReceiverBuilder::build`, rx/builder.rs:73-76 / receiver.rs:502-560), resident on
  * one GPU.  All channels advance in lockstep: one call processes `n_samples` samples of
- * every channel through the whole link layer (receiver.rs:343-474).
+ * every channel through the whole link layer (receiver.rs:343-474).  The ragged calls
+ * (same_batch_process_*_ragged, below) advance each channel by its own count instead.
  *
  * Input layout (f32 PCM, unscaled i16-range values as the reference expects,
  * lib.rs:78-81).  TIME_MAJOR is the native, coalesced layout:
@@ -309,6 +310,33 @@ int same_batch_process_device_i16(same_batch *rx, const int16_t *d_x, size_t n_s
 /* host-buffer convenience: copies to the device, processes, synchronises */
 int same_batch_process_host(same_batch *rx, const float *h_x, size_t n_samples, uint32_t layout);
 int same_batch_process_host_i16(same_batch *rx, const int16_t *h_x, size_t n_samples, uint32_t layout);
+/* Ragged calls: each channel fed its own number of samples, as N `SameReceiver`s fed independently (SameReceiver::process /
+ * iter_events, receiver.rs:119-161, 233-274).  `counts` is a HOST array of n_channels entries, counts[c] <= n_rows, read during
+ * the call and not kept.  The buffer has a plain call's shape with n_samples = n_rows (x[t * C + c] or x[c * n_rows + t]);
+ * channel c consumes only its first counts[c] samples, and the rows behind that are never read as samples (they may hold
+ * anything, NaN included).
+ *   - A call is exactly what counts[c] samples of SameReceiver::process do to receiver c, for every channel: each channel's
+ *     events count in its own samples, same_batch_channel_input_sample_counter(c) advances by counts[c], and
+ *     same_batch_input_sample_counter by M = max_c counts[c] (the batch's clock: the rows the call spans).
+ *   - counts[c] == 0 leaves channel c where it is; all counts zero is a no-op.  Counts that all equal n_rows make exactly the
+ *     plain call on the same buffer (same kernels, events and counters).
+ *   - Stream and input-lifetime contracts are those of the plain calls.  same_batch_flush, same_batch_reset and
+ *     same_batch_reset_channels may come between ragged and plain calls; strict, SAME_BATCH_RELAXED, SAME_BATCH_LINK_ONLY,
+ *     SAME_BATCH_GENERIC_KERNEL and SAME_BATCH_MESSAGES_ONLY batches (the transport layer on the device: a channel's messages,
+ *     forced end of message and same_batch_set_audio_capture chunks are those of its own samples), f32 and int16, both layouts
+ *     are supported.
+ *   - SAME_EINVAL, consuming nothing and leaving every counter as it was: counts == NULL, any counts[c] > n_rows, and batches
+ *     made with SAME_BATCH_TIME_PARALLEL (its planner cuts one common row range into pieces), SAME_BATCH_CALL_INVARIANT (its
+ *     windows begin at positions of one common stream) or SAME_BATCH_TRACE_SYMBOLS (the trace records batch positions).
+ *   - Cost: the first m = min_c counts[c] rows run through the batch's own lockstep kernels, the rows [m, M) through a ragged
+ *     form of the any-configuration kernel in the same launch -- the cost grows with M - m. */
+int same_batch_process_device_ragged(same_batch *rx, const float *d_x, size_t n_rows, const uint32_t *counts,
+                                     uint32_t layout, void *hip_stream);
+int same_batch_process_device_ragged_i16(same_batch *rx, const int16_t *d_x, size_t n_rows, const uint32_t *counts,
+                                         uint32_t layout, void *hip_stream);
+int same_batch_process_host_ragged(same_batch *rx, const float *h_x, size_t n_rows, const uint32_t *counts, uint32_t layout);
+int same_batch_process_host_ragged_i16(same_batch *rx, const int16_t *h_x, size_t n_rows, const uint32_t *counts,
+                                       uint32_t layout);
 /* SameReceiver::flush (receiver.rs:216-224): 4 * input_rate zero samples per channel.
  * Unlike the reference it does not stop at the first message; all events are reported. */
 int same_batch_flush(same_batch *rx);

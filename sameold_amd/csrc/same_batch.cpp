@@ -256,6 +256,11 @@ struct same_batch {
         // channels re-initialised in front of this launch (same_batch_reset_channels): pinned, mapped, read by the reset kernel
         uint32_t *h_reset = nullptr, *h_reset_dev = nullptr;
         uint32_t reset_cap = 0;
+        // a ragged call's per-channel counts (same_batch_process_*_ragged): pinned, mapped, read in place by the ragged kernel
+        uint32_t *h_counts = nullptr, *h_counts_dev = nullptr;
+        uint32_t counts_cap = 0;
+        // the wake table as uploaded behind the launch after this slot's harvest (batches that ran ragged launches)
+        uint64_t *h_wake_up = nullptr;
         // SAME_BATCH_MESSAGES_ONLY: the launch's message log (same_transport.hip; its cursor is d_counters[3]) and its landing buffer
         bool dev_transport = false;      // this launch ran the transport layer on the device
         // (its first records land in host-mapped pinned memory, read in place; the rest in HBM, copied when there are any)
@@ -365,6 +370,11 @@ struct same_batch {
     std::vector<same::TransportCold> tcold;
     same::TransportRef tr(uint32_t c) { return same::TransportRef(thot[c], tcold[c]); }
     uint64_t *h_wake = nullptr;      // host mirror of State::wake_sample (pinned, n_channels words, zero = unarmed)
+    // A ragged launch moves the device's wake-up instants itself (the ragged kernel), in stream order.  From the first one on the
+    // host's re-arming of the table is stream-ordered as well (behind the launch in flight, with its shifts added), so that an
+    // upload can no longer land across a ragged launch and undo its shift.
+    bool wake_ordered = false;
+    std::vector<uint32_t> ragged_by;  // scratch: the counter shifts of the ragged launch being queued
     // SAME_BATCH_MESSAGES_ONLY: only MSG_START / MSG_END are queued; unless the batch is time-parallel the transport layer runs on
     // the device (same_transport.hip) over per-channel records in HBM, and the device arms State::wake_sample itself
     bool messages_only = false;
@@ -1105,8 +1115,11 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
         const int arc = harvest_audio(rx, sl);
         if (arc) return arc;
     }
-    // the harvest has reached the resets asked for behind this launch: their host half (the counter bases) is due
     const int si = (int)(&sl - rx->slot);
+    // a ragged launch's counter shifts (the device moved its own forced-EOM instants), before the resets at the same position
+    rx->resets.shift_due(si);
+    rx->resets.done_shift(si);
+    // the harvest has reached the resets asked for behind this launch: their host half (the counter bases) is due
     // (the open captures of the channels end there, in their counters before the reset)
     if (const int arc = audio_end_reset(rx, rx->resets.slot[si & 1].channels, rx->resets.rec_pos(si))) return arc;
     for (uint32_t c : rx->resets.host_due(si)) reset_channel_host(rx, c, rx->resets.rec_pos(si));
@@ -1116,6 +1129,31 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         std::fprintf(stderr, "[same] harvest timing: wait %.2f ms, copy %.2f ms, %u messages queued in %.2f ms (transport layer on the device)\n",
                      ms(t_begin, t_waited), ms(t_waited, t_copied), n_msgs, ms(t_copied, t_end));
+    }
+    return SAME_OK;
+}
+
+// The wake table re-armed in stream order (batches that ran ragged launches): the launch still in flight, if any, moves its
+// channels' instants on the device as it ends (demod_ragged_kernel), so the table goes in behind it with that launch's shifts
+// added -- what the device would hold had the host's values been there before it.  The copy is queued on that launch's stream
+// and its done event moves behind the copy (later launches, harvests and the input-lifetime contract wait for that event).
+// The pinned source is the harvested slot's: the next write to it is that slot's next harvest, behind the copy.
+int upload_wake_ordered(same_batch *rx, same_batch::Slot &sl)
+{
+    const uint32_t C = rx->P.n_channels;
+    if (!sl.h_wake_up) HIP_TRY(hipHostMalloc((void **)&sl.h_wake_up, (size_t)C * sizeof(uint64_t), hipHostMallocDefault));
+    same_batch::Slot &other = rx->slot[(&sl - rx->slot) ^ 1];
+    const int oi = (int)(&other - rx->slot);
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint64_t w = rx->h_wake[c];
+        sl.h_wake_up[c] = w && other.in_flight ? w + rx->resets.pending_shift(oi, c) : w;
+    }
+    if (other.in_flight) {
+        HIP_TRY(hipMemcpyAsync(rx->S.wake_sample, sl.h_wake_up, (size_t)C * sizeof(uint64_t), hipMemcpyHostToDevice, rx->last_stream));
+        HIP_TRY(hipEventRecord(other.ev_done, rx->last_stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(rx->S.wake_sample, sl.h_wake_up, (size_t)C * sizeof(uint64_t), hipMemcpyHostToDevice, rx->copy_stream));
+        HIP_TRY(hipStreamSynchronize(rx->copy_stream));
     }
     return SAME_OK;
 }
@@ -1171,6 +1209,16 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     HarvestTimes times;
     int rc = harvest_host(rx, sl, n_events, n_bursts, rearm, times);
     if (rc) return rc;
+    // a ragged launch's counter shifts are due now that its own events are replayed: the channels' armed forced-EOM instants
+    // move with them (and are re-armed), then the queued records' counter bases
+    {
+        const int si = (int)(&sl - rx->slot);
+        const same::ResetLedger::SlotShift &sh = rx->resets.shift_due(si);
+        if (!rx->thot.empty())
+            for (size_t i = 0; i < sh.channels.size(); ++i)
+                if (rx->tr(sh.channels[i]).shift_force_eom(sh.by[i])) rearm.push_back(sh.channels[i]);
+        rx->resets.done_shift(si);
+    }
     // the harvest has reached the resets asked for behind this launch: their host half is due (before the wake table is
     // re-armed below, so that a reset channel's entry goes back to the device as 0)
     {
@@ -1190,10 +1238,15 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
             std::memset(rx->h_wake, 0, (size_t)rx->P.n_channels * sizeof(uint64_t));
         }
         for (uint32_t c : rearm) rx->h_wake[c] = rx->tr(c).force_eom_at();
+        if (rx->wake_ordered) {
+            int rc2 = upload_wake_ordered(rx, sl);
+            if (rc2) return rc2;
+        } else {
         // the kernels only read this table (it is host-owned), so it may be updated while a
         // later launch runs; launches are capped at 45 s, two launches < the 135 s timeout
         HIP_TRY(hipMemcpyAsync(rx->S.wake_sample, rx->h_wake, (size_t)rx->P.n_channels * sizeof(uint64_t), hipMemcpyHostToDevice, rx->copy_stream));
         HIP_TRY(hipStreamSynchronize(rx->copy_stream));
+        }
     }
     if (dbg) {
         auto t_end = std::chrono::steady_clock::now();
@@ -1384,8 +1437,16 @@ int ensure_wide_state(same_batch *rx, uint32_t columns)
     return SAME_OK;
 }
 
+// A ragged call (same_batch_process_*_ragged) as the launches of one time-major piece see it: the call's per-channel counts
+// (host, n_channels entries), the smallest of them and the call row of the piece's first row
+struct Ragged {
+    const uint32_t *counts = nullptr;
+    uint32_t m = 0;
+    uint32_t row_off = 0;
+};
+
 template <typename SampleT>
-int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_samples, hipStream_t stream)
+int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_samples, hipStream_t stream, const Ragged *rg = nullptr)
 {
     // keep one launch comfortably inside u32 sample indices and bounded output pools, and
     // well under the 135 s forced-EOM timeout the host arms one launch late (harvest)
@@ -1401,9 +1462,31 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
         rc = launch_pending_resets(rx, sl, stream);
         if (rc) return rc;
+        // a ragged call: rows [0, n_lock) of this launch are every channel's (the common prefix: the lockstep kernels below),
+        // rows [n_lock, n) only some channels' (the ragged kernel, behind them in the same launch)
+        size_t n_lock = n;
+        if (rg) {
+            const size_t row0 = (size_t)rg->row_off + done;
+            n_lock = rg->m > row0 ? std::min<size_t>(rg->m - row0, n) : 0;
+            const uint32_t C = rx->P.n_channels;
+            if (C > sl.counts_cap) {
+                if (sl.h_counts) HIP_TRY(hipHostFree(sl.h_counts));
+                sl.h_counts = nullptr; sl.h_counts_dev = nullptr; sl.counts_cap = 0;
+                HIP_TRY(hipHostMalloc((void **)&sl.h_counts, (size_t)C * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+                HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_counts_dev, sl.h_counts, 0));
+                sl.counts_cap = C;
+            }
+            // (the slot's previous launch, the last reader of this buffer, has been harvested above)
+            std::memcpy(sl.h_counts, rg->counts, (size_t)C * sizeof(uint32_t));
+            rx->ragged_by.resize(C);
+            for (uint32_t c = 0; c < C; ++c) {
+                const size_t have = rg->counts[c] > row0 ? std::min<size_t>(rg->counts[c] - row0, n) : 0;
+                rx->ragged_by[c] = (uint32_t)(n - have);
+            }
+        }
         same::ChunkGeom geom{};
         same::PipeChunks pc{};
-        const uint32_t n_chunks = plan_chunks(rx, n, geom, pc);
+        const uint32_t n_chunks = rg ? 1u : plan_chunks(rx, n, geom, pc);
         rx->tp.last_chunks = n_chunks;
         sl.have_k = false;
         bool sort_bins_empty = false;          // the launch's prologue kernel has emptied the event sort's bins
@@ -1499,7 +1582,7 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         rx->last_plain_fm = plain_fm; rx->last_plain_wave = plain_wave;
         const size_t fb = plain_fm ? fm_block_len(Pfm)
                                    : (plain_wave ? same::relaxed_block_len(rx->P) : (rx->use_fast ? same::fast_block_len(rx->P) : 16));
-        size_t n_fast = (rx->use_fast && !rx->force_generic) ? (n / fb) * fb : 0;
+        size_t n_fast = (rx->use_fast && !rx->force_generic) ? (n_lock / fb) * fb : 0;
         if (n_fast && plain_fm) {
             e = launch_fm(Pfm, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream, same::PipeChunks{});
             rx->last_fm_sym = same::sym_kernel_supported(Pfm);
@@ -1520,13 +1603,25 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
                          : same::launch_demod_fast_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xp, (uint32_t)(n_fast / fb), rx->counter, stream);
             if (e != hipSuccess) return fail(SAME_EHIP, "fast demod kernel launch failed: %s", hipGetErrorString(e));
         }
-        if (n_fast < n) {
+        if (n_fast < n_lock) {
             const SampleT *xr = xp + n_fast * rx->P.n_channels;
             if constexpr (sizeof(SampleT) == 4)
-                e = same::launch_demod(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n - n_fast), rx->counter + n_fast, stream);
+                e = same::launch_demod(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n_lock - n_fast), rx->counter + n_fast, stream);
             else
-                e = same::launch_demod_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n - n_fast), rx->counter + n_fast, stream);
+                e = same::launch_demod_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n_lock - n_fast), rx->counter + n_fast, stream);
             if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
+        }
+        if (n_lock < n) {
+            // the ragged remainder: each lane its own count, the state left canonical at the launch's end
+            const SampleT *xr = xp + n_lock * rx->P.n_channels;
+            const uint32_t sub = (uint32_t)(rg->row_off + done + n_lock);
+            if constexpr (sizeof(SampleT) == 4)
+                e = same::launch_demod_ragged(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n - n_lock), sl.h_counts_dev, sub,
+                                              rx->counter + n_lock, stream);
+            else
+                e = same::launch_demod_ragged_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n - n_lock), sl.h_counts_dev,
+                                                  sub, rx->counter + n_lock, stream);
+            if (e != hipSuccess) return fail(SAME_EHIP, "ragged demod kernel launch failed: %s", hipGetErrorString(e));
         }
         }
         if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
@@ -1556,7 +1651,10 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
                 K.n_spans = &sl.d_cap_cur->n_spans; K.pool_used = &sl.d_cap_cur->pool_used; K.pool_cap = rx->audio.per_launch;
                 K.overflow = &sl.d_cap_cur->overflow;
             }
-            HIP_TRY(same::launch_transport(T, stream));
+            if (rg && n_lock < n)
+                HIP_TRY(same::launch_transport_ragged(T, sl.h_counts_dev, (uint32_t)(rg->row_off + done), (uint32_t)n, stream));
+            else
+                HIP_TRY(same::launch_transport(T, stream));
             if (sl.captured) {
                 const SampleT *xc = d_x + done * rx->P.n_channels;
                 hipError_t e;
@@ -1574,6 +1672,8 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         sl.in_flight = true;
         sl.seq = ++rx->launch_seq;
         rx->last_stream = stream;
+        // a ragged launch: the channels that consumed fewer than n rows lag the batch by that much more from here on
+        if (rg) rx->resets.shift(rx->ragged_by.data(), rx->counter + n, (int)(&sl - rx->slot));
         rx->counter += n;
         sl.end_counter = rx->counter;
         done += n;
@@ -1983,6 +2083,120 @@ int process_host_any(same_batch *rx, const SampleT *h_x, size_t n_samples, uint3
     return rc;
 }
 
+// A ragged call (same_batch_process_*_ragged, include/same_rx.h): channel c consumes the first counts[c] of the buffer's n_rows
+// rows.  The common prefix (the smallest count) runs through the batch's lockstep kernels, the rows up to the largest count
+// through the ragged kernel in the same launch; the per-channel counter shifts go to the ledger.
+int ragged_check(same_batch *rx, size_t n_rows, const uint32_t *counts, uint32_t layout, uint32_t *m_out, uint32_t *M_out)
+{
+    if (!rx) return fail(SAME_EINVAL, "null handle");
+    if (!counts) return fail(SAME_EINVAL, "null counts");
+    if (layout != SAME_LAYOUT_TIME_MAJOR && layout != SAME_LAYOUT_CHANNEL_MAJOR) return fail(SAME_EINVAL, "unknown layout %u", layout);
+    if (rx->tp.enabled) return fail(SAME_EINVAL, "ragged calls: a SAME_BATCH_TIME_PARALLEL batch plans its cuts over one common row range");
+    if (rx->inv.on) return fail(SAME_EINVAL, "ragged calls: SAME_BATCH_CALL_INVARIANT windows begin at positions of one common stream");
+    if (rx->P.trace_cap) return fail(SAME_EINVAL, "ragged calls: SAME_BATCH_TRACE_SYMBOLS records batch sample positions");
+    if (n_rows > 0xffffffffull) return fail(SAME_EINVAL, "ragged calls: n_rows beyond 2^32 - 1");
+    uint32_t m = UINT32_MAX, M = 0;
+    for (uint32_t c = 0; c < rx->P.n_channels; ++c) {
+        if (counts[c] > n_rows) return fail(SAME_EINVAL, "counts[%u] = %u exceeds n_rows = %zu; nothing was consumed", c, counts[c], n_rows);
+        m = std::min(m, counts[c]); M = std::max(M, counts[c]);
+    }
+    *m_out = m; *M_out = M;
+    return SAME_OK;
+}
+
+// The rows [row_base, row_base + n_buf) of a ragged call, in a buffer of their own (channel-major: row pitch `pitch`), as far as
+// they reach into [0, M)
+template <typename SampleT>
+int process_ragged_on(same_batch *rx, const SampleT *d_x, size_t pitch, size_t n_buf, size_t row_base, const uint32_t *counts,
+                      uint32_t m, uint32_t M, uint32_t layout, hipStream_t stream)
+{
+    const uint32_t C = rx->P.n_channels;
+    const size_t n_p = std::min<size_t>(M, row_base + n_buf) - row_base;
+    Ragged rg; rg.counts = counts; rg.m = m;
+    if (layout == SAME_LAYOUT_TIME_MAJOR) {
+        // (read in place: rows at stride C)
+        if (m == M) return process_time_major_launches(rx, d_x, n_p, stream);
+        rg.row_off = (uint32_t)row_base;
+        return process_time_major_launches(rx, d_x, n_p, stream, &rg);
+    }
+    // channel-major: every row's samples, in slabs, through the staging buffers into time-major
+    for (same_batch::Slot &sl : rx->slot)
+        if (sl.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sl.ev_done, 0));
+    const size_t slab = std::min<size_t>(n_p, (size_t)65520);
+    int rc = ensure_stage(&rx->d_stage2, &rx->stage2_bytes, slab * C * sizeof(SampleT));
+    if (rc) return rc;
+    for (size_t t0 = 0; t0 < n_p; t0 += slab) {
+        const size_t n = std::min(slab, n_p - t0);
+        rc = ensure_stage(&rx->d_stage, &rx->stage_bytes, n * C * sizeof(SampleT));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy2DAsync(rx->d_stage, n * sizeof(SampleT), d_x + t0, pitch * sizeof(SampleT), n * sizeof(SampleT), C,
+                                 hipMemcpyDeviceToDevice, stream));
+        hipError_t e;
+        if constexpr (sizeof(SampleT) == 4)
+            e = same::launch_transpose_f32((const float *)rx->d_stage, (float *)rx->d_stage2, C, (uint32_t)n, stream);
+        else
+            e = same::launch_transpose_i16((const int16_t *)rx->d_stage, (int16_t *)rx->d_stage2, C, (uint32_t)n, stream);
+        if (e != hipSuccess) return fail(SAME_EHIP, "transpose launch failed: %s", hipGetErrorString(e));
+        if (m == M) {
+            rc = process_time_major_launches(rx, (const SampleT *)rx->d_stage2, n, stream);
+        } else {
+            rg.row_off = (uint32_t)(row_base + t0);
+            rc = process_time_major_launches(rx, (const SampleT *)rx->d_stage2, n, stream, &rg);
+        }
+        if (rc) return rc;
+    }
+    return SAME_OK;
+}
+
+template <typename SampleT>
+int process_ragged_device(same_batch *rx, const SampleT *d_x, size_t n_rows, const uint32_t *counts, uint32_t layout, void *hip_stream)
+{
+    uint32_t m = 0, M = 0;
+    int rc = ragged_check(rx, n_rows, counts, layout, &m, &M);
+    if (rc) return rc;
+    if (M == 0) return SAME_OK;
+    if (!d_x) return fail(SAME_EINVAL, "null argument");
+    // every channel all n_rows: exactly the plain call
+    if (m == M && M == n_rows) return process_device_any(rx, d_x, n_rows, layout, hip_stream);
+    HIP_TRY(hipSetDevice(rx->device));
+    hipStream_t stream = hip_stream == SAME_STREAM_OWN ? rx->own_stream : (hipStream_t)hip_stream;
+    if (m != M) rx->wake_ordered = true;
+    return process_ragged_on(rx, d_x, n_rows, n_rows, 0, counts, m, M, layout, stream);
+}
+
+template <typename SampleT>
+int process_ragged_host(same_batch *rx, const SampleT *h_x, size_t n_rows, const uint32_t *counts, uint32_t layout)
+{
+    uint32_t m = 0, M = 0;
+    int rc = ragged_check(rx, n_rows, counts, layout, &m, &M);
+    if (rc) return rc;
+    if (M == 0) return SAME_OK;
+    if (!h_x) return fail(SAME_EINVAL, "null argument");
+    if (m == M && M == n_rows) return process_host_any(rx, h_x, n_rows, layout);
+    HIP_TRY(hipSetDevice(rx->device));
+    if (m != M) rx->wake_ordered = true;
+    // upload the first M rows in slabs, as process_host_any does, so that long calls need bounded device memory
+    const size_t C = rx->P.n_channels;
+    const size_t slab = std::max<size_t>(1, std::min<size_t>(M, ((size_t)256 << 20) / (C * sizeof(SampleT))));
+    rc = ensure_stage(&rx->d_upload, &rx->upload_bytes, slab * C * sizeof(SampleT));
+    if (rc) return rc;
+    // (the upload buffer may still be read by a launch in flight: every launch of the batch is collected first)
+    rc = harvest(rx);
+    for (size_t t0 = 0; t0 < M && rc == SAME_OK; t0 += slab) {
+        const size_t n = std::min<size_t>(slab, M - t0);
+        hipError_t e = layout == SAME_LAYOUT_TIME_MAJOR
+                           ? hipMemcpy(rx->d_upload, h_x + t0 * C, n * C * sizeof(SampleT), hipMemcpyHostToDevice)
+                           : hipMemcpy2D(rx->d_upload, n * sizeof(SampleT), h_x + t0, n_rows * sizeof(SampleT), n * sizeof(SampleT), C,
+                                         hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = fail(SAME_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
+        rc = process_ragged_on(rx, (const SampleT *)rx->d_upload, n, n, t0, counts, m, M, layout, rx->own_stream);
+        if (rc == SAME_OK) rc = harvest(rx);
+    }
+    if (rc == SAME_OK && rx->kernel_fault) return fail(SAME_EKERNEL, "a demodulation kernel's wavefronts lost step (internal hand-over timed out)");
+    if (rc == SAME_OK && rx->overflowed) return fail(SAME_EOVERFLOW, "event/burst pool overflow");
+    return rc;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------
@@ -2126,6 +2340,8 @@ void same_batch_free(same_batch *rx)
         if (sl.d_geom) (void)hipFree(sl.d_geom);
         if (sl.h_geom) (void)hipHostFree(sl.h_geom);
         if (sl.h_reset) (void)hipHostFree(sl.h_reset);
+        if (sl.h_counts) (void)hipHostFree(sl.h_counts);
+        if (sl.h_wake_up) (void)hipHostFree(sl.h_wake_up);
         if (sl.d_msgs) (void)hipFree(sl.d_msgs);
         if (sl.h_near) (void)hipHostFree(sl.h_near);
         if (sl.h_msgs) (void)hipHostFree(sl.h_msgs);
@@ -2243,6 +2459,16 @@ int same_batch_process_host(same_batch *rx, const float *h_x, size_t n_samples, 
 { return process_host_any<float>(rx, h_x, n_samples, layout); }
 int same_batch_process_host_i16(same_batch *rx, const int16_t *h_x, size_t n_samples, uint32_t layout)
 { return process_host_any<int16_t>(rx, h_x, n_samples, layout); }
+
+int same_batch_process_device_ragged(same_batch *rx, const float *d_x, size_t n_rows, const uint32_t *counts, uint32_t layout, void *hip_stream)
+{ return process_ragged_device<float>(rx, d_x, n_rows, counts, layout, hip_stream); }
+int same_batch_process_device_ragged_i16(same_batch *rx, const int16_t *d_x, size_t n_rows, const uint32_t *counts, uint32_t layout,
+                                         void *hip_stream)
+{ return process_ragged_device<int16_t>(rx, d_x, n_rows, counts, layout, hip_stream); }
+int same_batch_process_host_ragged(same_batch *rx, const float *h_x, size_t n_rows, const uint32_t *counts, uint32_t layout)
+{ return process_ragged_host<float>(rx, h_x, n_rows, counts, layout); }
+int same_batch_process_host_ragged_i16(same_batch *rx, const int16_t *h_x, size_t n_rows, const uint32_t *counts, uint32_t layout)
+{ return process_ragged_host<int16_t>(rx, h_x, n_rows, counts, layout); }
 
 int same_batch_flush(same_batch *rx)
 {

@@ -92,15 +92,21 @@ SAME_HD inline void or_u32(uint32_t *p, uint32_t v)
 }
 
 // One channel's walk over its messages of one launch: on_message() for each (in order), then finish().
-struct Walker {
+// RAGGED (a ragged launch, same_batch_process_*_ragged): the channel consumed only the launch's first `rows` rows, and its
+// captures stop there; the other rows are not its samples.
+template <bool RAGGED>
+struct WalkerT {
     const Launch &L;
     uint32_t c;
     Rec r;
+    uint32_t rows = 0;
 
-    SAME_HD Walker(const Launch &l, uint32_t channel) : L(l), c(channel), r(l.rec ? l.rec[channel] : Rec{0, 0, 0}) {}
+    SAME_HD WalkerT(const Launch &l, uint32_t channel) : L(l), c(channel), r(l.rec ? l.rec[channel] : Rec{0, 0, 0}) {}
+    SAME_HD WalkerT(const Launch &l, uint32_t channel, uint32_t own_rows) : L(l), c(channel), r(l.rec ? l.rec[channel] : Rec{0, 0, 0}), rows(own_rows) {}
+    SAME_HD uint32_t n_rows() const { return RAGGED ? rows : L.n_rows; }
     SAME_HD bool has_flush() const { return L.flush_row != kNoFlush; }
-    SAME_HD uint64_t real_end() const { return L.start + (has_flush() ? L.flush_row : L.n_rows); }      // end of the rows that may be captured
-    SAME_HD uint64_t clamp(uint64_t m) const { return m < L.start ? L.start : (m > L.start + L.n_rows ? L.start + L.n_rows : m); }
+    SAME_HD uint64_t real_end() const { return L.start + (has_flush() ? L.flush_row : n_rows()); }      // end of the rows that may be captured
+    SAME_HD uint64_t clamp(uint64_t m) const { return m < L.start ? L.start : (m > L.start + n_rows() ? L.start + n_rows() : m); }
     SAME_HD uint64_t from() const { return r.from < L.start ? L.start : r.from; }
 
     // the chunk [a, b) (counters, inside [start, real_end()]) with `flags`
@@ -146,6 +152,7 @@ struct Walker {
         L.rec[c] = r;
     }
 };
+using Walker = WalkerT<false>;
 
 }  // namespace cap
 }  // namespace same

@@ -13,6 +13,13 @@ hipError_t launch_demod(const Params &P, const State &S, const Output &O, const 
 hipError_t launch_demod_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
                             const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
 size_t demod_lds_bytes(const Params &P);
+// the ragged remainder of a ragged call (same_batch_process_*_ragged): rows [0, n_rows) of x, lane c consuming its first
+// min(counts[c] - row_sub, n_rows) of them (counts: device-readable, n_channels entries); leaves the state canonical at
+// counter0 + n_rows
+hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
+                               uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
+hipError_t launch_demod_ragged_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                                   uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
 // latency-optimised kernel for the standard rates (same_kernels_fast.hip); whole blocks of
 // fast_block_len() samples, the generic kernel takes the rest of a call
 // longest block that can hold at most one TED instant for this configuration (same_config.cpp)
@@ -126,6 +133,9 @@ struct TransportLaunch {
 size_t transport_hot_bytes();
 size_t transport_cold_bytes();
 hipError_t launch_transport(const TransportLaunch &T, hipStream_t stream);
+// a ragged launch (same_batch_process_*_ragged): channel c consumed the first min(counts[c] - row_sub, n_rows) of the launch's
+// n_rows rows (counts: device-readable); its captures stop there and an armed forced-EOM instant moves by the rows it skipped
+hipError_t launch_transport_ragged(const TransportLaunch &T, const uint32_t *counts, uint32_t row_sub, uint32_t n_rows, hipStream_t stream);
 // reset() of the transport layer of the columns cols[0 .. n) (device-readable), or of every channel (cols == nullptr); fresh: the
 // records were never written (a new batch); capture_rec: the channels' capture records (cap::Rec), closed too, or nullptr
 hipError_t launch_transport_reset(void *hot, void *cold, uint32_t n_channels, const uint32_t *cols, uint32_t n, int fresh,

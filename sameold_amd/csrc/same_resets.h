@@ -6,7 +6,9 @@
 //   - the host state of the channel (transport layer, time-parallel symbol clock, wake-up instant): once the harvest has
 //     replayed the last launch before the position -- that launch may still be running when the reset is asked for;
 //   - the sample counter of the channel's queued events: they count from the position on, from the same instant.
-// Host-only (no HIP): tests/helpers/reset_ledger_main.cpp drives it under ASan + UBSan without a device.
+// A ragged launch (same_batch_process_*_ragged) leaves some channels behind the batch's counter: their counter bases move by the
+// rows they did not consume, with the same two halves (ResetLedger::shift).
+// Host-only (no HIP): tests/helpers/reset_ledger_main.cpp and ragged_ledger_main.cpp drive it under ASan + UBSan without a device.
 #ifndef SAME_RESETS_H
 #define SAME_RESETS_H
 
@@ -35,6 +37,7 @@ struct ResetLedger {
         rec_base.assign(n_channels, 0);
         device.clear();
         for (SlotResets &s : slot) { s.channels.clear(); s.pos = 0; }
+        for (SlotShift &h : shift_) { h.channels.clear(); h.by.clear(); h.pos = 0; }
     }
     // the whole batch was reset (same_batch_reset): the stream starts again at 0 for every channel
     void clear() { init((uint32_t)api_base.size()); }
@@ -88,6 +91,35 @@ struct ResetLedger {
         return r.channels;
     }
     void done_host(int s) { slot[s & 1].channels.clear(); }
+
+    // A ragged launch (same_batch_process_*_ragged) in slot `s` that ends at stream position `pos` and gave channel c only
+    // n - by[c] of its n rows: the channel's own stream lags the batch's by by[c] more from `pos` on, i.e. its counter base
+    // moves by by[c] there.  The caller's view moves at once; the queued records' when the harvest has replayed the launch
+    // (its own records still count with the old base).  `by`: n_channels entries.
+    struct SlotShift { std::vector<uint32_t> channels, by; uint64_t pos = 0; };
+    SlotShift shift_[2];
+    void shift(const uint32_t *by, uint64_t pos, int s)
+    {
+        SlotShift &h = shift_[s & 1];
+        h.channels.clear(); h.by.clear(); h.pos = pos;
+        for (uint32_t c = 0; c < (uint32_t)api_base.size(); ++c)
+            if (by[c]) { api_base[c] += by[c]; h.channels.push_back(c); h.by.push_back(by[c]); }
+    }
+    // the harvest has replayed slot `s`: its shifts are due (before its resets, which lie at the same position and win)
+    const SlotShift &shift_due(int s)
+    {
+        SlotShift &h = shift_[s & 1];
+        for (size_t i = 0; i < h.channels.size(); ++i) rec_base[h.channels[i]] += h.by[i];
+        return h;
+    }
+    void done_shift(int s) { shift_[s & 1].channels.clear(); shift_[s & 1].by.clear(); }
+    // the shift of slot `s` still to come for channel c (0 if none): a launch in flight that the harvest has not reached
+    uint32_t pending_shift(int s, uint32_t c) const
+    {
+        const SlotShift &h = shift_[s & 1];
+        auto it = std::lower_bound(h.channels.begin(), h.channels.end(), c);
+        return it != h.channels.end() && *it == c ? h.by[(size_t)(it - h.channels.begin())] : 0u;
+    }
     uint64_t rec_pos(int s) const { return slot[s & 1].pos; }
 
     // sample counter of a record of channel c as queued: the device counts from the batch's first sample

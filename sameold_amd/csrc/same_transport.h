@@ -118,6 +118,9 @@ public:
     // force_eom_at_sample (receiver.rs:89): 0 = None
     uint64_t force_eom_at() const { return h_.have_force_eom ? h_.force_eom_at : 0; }
     bool force_eom_dirty() { const bool d = h_.dirty != 0; h_.dirty = 0; return d; }
+    // a ragged launch left the channel `by` samples further behind the batch's counter: an armed instant (batch sample
+    // coordinates) moves with it; true if there was one (it has to be re-armed on the device)
+    bool shift_force_eom(uint64_t by) { if (!h_.have_force_eom || !by) return false; h_.force_eom_at += by; return true; }
 
 private:
     // Assembler: both return the TransportState kind and fill *msg for Message states

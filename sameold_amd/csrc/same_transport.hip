@@ -65,6 +65,60 @@ __global__ __launch_bounds__(64) void transport_kernel(TransportLaunch T)
     if (capture) w.finish();
 }
 
+// A ragged launch (same_batch_process_*_ragged): transport_kernel's lane, where channel c consumed only the first
+// k = min(counts[c] - row_sub, n_rows) of the launch's n_rows rows and lags the batch by n_rows - k more when it ends.  Its
+// captures stop at its own end, and an armed forced-EOM instant (batch sample coordinates) moves with the lag.  (A function
+// of its own: transport_kernel's code stays exactly what it was.)
+__global__ __launch_bounds__(64) void transport_ragged_kernel(TransportLaunch T, const uint32_t *__restrict__ counts, uint32_t row_sub,
+                                                              uint32_t n_rows)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= T.n_channels) return;
+    const uint32_t want = counts[c];
+    const uint32_t own = want > row_sub ? min(want - row_sub, n_rows) : 0u;
+    const uint32_t b = T.first[c], e = T.first[c + 1u];
+    DevEvent *ev = T.sorted;
+    for (uint32_t i = b + 1u; i < e; ++i) {
+        const DevEvent x = ev[i];
+        uint32_t j = i;
+        while (j > b && ev[j - 1u].channel > x.channel) { ev[j] = ev[j - 1u]; --j; }
+        ev[j] = x;
+    }
+    const uint32_t n_bursts = min(T.counters[1], T.burst_cap);
+    dt::Hot *hot = static_cast<dt::Hot *>(T.hot);
+    dt::Hot h = hot[c];
+    dt::Transport tr{h, static_cast<dt::Cold *>(T.cold)[c]};
+    dt::Msg msg;
+    dt::Event out;
+    uint32_t seq = 0;
+    const bool capture = T.cap.rec != nullptr;
+    cap::WalkerT<true> w(T.cap, capture ? c : 0u, own);
+    for (uint32_t i = b; i < e; ++i) {
+        const DevEvent d = ev[i];
+        const uint8_t *bytes = nullptr;
+        uint32_t len = 0;
+        if (d.kind == SAME_LINK_BURST && d.burst_slot < n_bursts) {
+            bytes = T.bursts + (size_t)d.burst_slot * kBurstCap;
+            len = min(d.burst_len, (uint32_t)kBurstCap);
+        }
+        if (!tr.on_link_event(d.kind, d.sample_counter, d.symbol_count, bytes, len, T.input_rate, msg, &out)) continue;
+        if (out.kind != SAME_TRANSPORT_MSG_START && out.kind != SAME_TRANSPORT_MSG_END) continue;
+        if (capture) w.on_message(out.kind, out.sample_counter);
+        const uint32_t k = atomicAdd(T.log_cursor, 1u);
+        if (k >= T.near_cap && k - T.near_cap >= T.log_cap) { atomicOr(T.overflow, kMessageLogOverflow); continue; }
+        DevMessage &m = k < T.near_cap ? T.near[k] : T.log[k - T.near_cap];
+        m.channel = c; m.kind = out.kind; m.sample_counter = out.sample_counter; m.symbol_count = out.symbol_count;
+        m.len = out.len; m.aux = out.aux; m.aux2 = out.aux2; m.seq = seq++;
+        if (out.kind == SAME_TRANSPORT_MSG_START) dt::copy_bytes(m.text, out.text, out.len < kDevMessageText ? out.len : kDevMessageText);
+    }
+    // the instant in the coordinates after the launch (the ragged kernel in front of this one moved the device's copy by the
+    // lag already: this writes the same value, or the instant this launch armed)
+    const bool moved = tr.shift_force_eom(n_rows - own);
+    if (tr.force_eom_dirty() || moved) T.wake_sample[c] = tr.force_eom_at();
+    hot[c] = h;
+    if (capture) w.finish();
+}
+
 // SameReceiver::reset() of the transport layer (receiver.rs:195-196): the listed channels, or all of them (cols == nullptr)
 // (cap: the channels' capture records, or nullptr: an open capture ends at the reset -- the host queues its END_RESET chunk)
 __global__ __launch_bounds__(64) void transport_reset_kernel(dt::Hot *hot, dt::Cold *cold, uint32_t n_channels, const uint32_t *cols,
@@ -91,6 +145,13 @@ hipError_t launch_transport(const TransportLaunch &T, hipStream_t stream)
 {
     if (T.n_channels == 0) return hipSuccess;
     hipLaunchKernelGGL(transport_kernel, dim3((T.n_channels + 63u) / 64u), dim3(64), 0, stream, T);
+    return hipGetLastError();
+}
+
+hipError_t launch_transport_ragged(const TransportLaunch &T, const uint32_t *counts, uint32_t row_sub, uint32_t n_rows, hipStream_t stream)
+{
+    if (T.n_channels == 0) return hipSuccess;
+    hipLaunchKernelGGL(transport_ragged_kernel, dim3((T.n_channels + 63u) / 64u), dim3(64), 0, stream, T, counts, row_sub, n_rows);
     return hipGetLastError();
 }
 

@@ -209,6 +209,9 @@ struct Transport {
     // force_eom_at_sample (receiver.rs:89), 0 = None
     SAME_HD uint64_t force_eom_at() const { return h.have_force_eom ? h.force_eom_at : 0; }
     SAME_HD bool force_eom_dirty() { const bool d = h.dirty != 0; h.dirty = 0; return d; }
+    // a ragged launch left the channel `by` samples further behind the batch's counter: an armed instant (batch sample
+    // coordinates) moves with it; true if there was one
+    SAME_HD bool shift_force_eom(uint64_t by) { if (!h.have_force_eom || !by) return false; h.force_eom_at += by; return true; }
 
     // rx/assembler.rs:362-368: retain unexpired entries, then keep at most the two newest
     SAME_HD void prune_history(uint64_t now)

@@ -194,6 +194,10 @@ def load_library() -> C.CDLL:
     sig("same_batch_process_device_i16", C.c_int, vp, vp, C.c_size_t, u32, vp)
     sig("same_batch_process_host", C.c_int, vp, vp, C.c_size_t, u32)
     sig("same_batch_process_host_i16", C.c_int, vp, vp, C.c_size_t, u32)
+    sig("same_batch_process_device_ragged", C.c_int, vp, vp, C.c_size_t, P(u32), u32, vp)
+    sig("same_batch_process_device_ragged_i16", C.c_int, vp, vp, C.c_size_t, P(u32), u32, vp)
+    sig("same_batch_process_host_ragged", C.c_int, vp, vp, C.c_size_t, P(u32), u32)
+    sig("same_batch_process_host_ragged_i16", C.c_int, vp, vp, C.c_size_t, P(u32), u32)
     sig("same_batch_flush", C.c_int, vp)
     sig("same_batch_sync", C.c_int, vp)
     sig("same_batch_poll_events", C.c_int, vp, P(Event), C.c_size_t, P(C.c_size_t), P(C.c_size_t))
@@ -491,6 +495,57 @@ class SameBatchReceiver:
         else:
             x = np.ascontiguousarray(x, dtype=np.float32)
             _check(self._L.same_batch_process_host(self._h, C.c_void_p(x.ctypes.data), n, layout))
+
+    def _ragged_counts(self, counts):
+        """counts as the C ABI takes them: n_channels uint32 (a sequence, an ndarray or a CPU tensor)."""
+        if hasattr(counts, "detach"):
+            counts = counts.detach().cpu().numpy()
+        a = np.asarray(counts)
+        if a.ndim != 1 or a.shape[0] != self.n_channels:
+            raise SameError(-1, f"ragged call: {a.shape} counts for {self.n_channels} channels; nothing was consumed")
+        if a.size and (a.min() < 0 or a.max() > 0xffffffff):
+            raise SameError(-1, "ragged call: a count is out of range; nothing was consumed")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def process_ragged(self, x, counts, layout: int = LAYOUT_TIME_MAJOR, stream: Optional[int] = None):
+        """A ragged call (same_batch_process_device_ragged): x is a torch CUDA tensor, float32 or int16, [n_rows, C]
+        (time-major) or [C, n_rows]; channel c consumes only its first counts[c] samples (counts: n_channels entries, each
+        <= n_rows).  Stream and lifetime handling as in `process_tensor`."""
+        import torch
+        assert x.is_cuda and x.is_contiguous()
+        if layout == LAYOUT_TIME_MAJOR:
+            n, ch = x.shape
+        else:
+            ch, n = x.shape
+        assert ch == self.n_channels
+        if x.dtype not in (torch.float32, torch.int16):
+            raise TypeError("float32 or int16 input")
+        k = self._ragged_counts(counts)
+        if stream is None:
+            self.order_after(torch.cuda.current_stream(x.device).cuda_stream)
+        self._inflight.append(x)
+        fn = self._L.same_batch_process_device_ragged_i16 if x.dtype == torch.int16 else self._L.same_batch_process_device_ragged
+        try:
+            _check(fn(self._h, C.c_void_p(x.data_ptr()), n, k.ctypes.data_as(C.POINTER(C.c_uint32)), layout,
+                      C.c_void_p(STREAM_OWN if stream is None else stream)))
+        except SameError:
+            self._inflight.pop()
+            raise
+        if len(self._inflight) > 2:
+            del self._inflight[0]
+
+    def process_host_ragged(self, x: np.ndarray, counts, layout: int = LAYOUT_TIME_MAJOR):
+        """A ragged call on a host array (same_batch_process_host_ragged): numpy float32 / int16, [n_rows, C] or [C, n_rows]."""
+        x = np.ascontiguousarray(x)
+        n, ch = x.shape if layout == LAYOUT_TIME_MAJOR else x.shape[::-1]
+        assert ch == self.n_channels, (ch, self.n_channels)
+        k = self._ragged_counts(counts)
+        kp = k.ctypes.data_as(C.POINTER(C.c_uint32))
+        if x.dtype == np.int16:
+            _check(self._L.same_batch_process_host_ragged_i16(self._h, C.c_void_p(x.ctypes.data), n, kp, layout))
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            _check(self._L.same_batch_process_host_ragged(self._h, C.c_void_p(x.ctypes.data), n, kp, layout))
 
     def flush(self):
         _check(self._L.same_batch_flush(self._h))
