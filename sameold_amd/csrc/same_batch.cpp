@@ -25,6 +25,7 @@
 #include "../../include/same_rx.h"
 #include "same_config.h"
 #include "same_device.h"
+#include "same_hipmem.h"
 #include "same_launch.h"
 #include "same_resets.h"
 #include "same_transport.h"
@@ -214,31 +215,30 @@ struct same_batch {
     uint64_t counter = 0;            // input_sample_counter (common to all channels)
     hipStream_t own_stream = nullptr;
     hipStream_t last_stream = nullptr;
-    float4 *d_taps = nullptr;
-    void *d_state_blob = nullptr;    // one allocation backing every State array
-    size_t state_bytes = 0;
+    same::DevBuf<float4> d_taps;
+    same::DevBuf<void> d_state_blob; // one allocation backing every State array
     // Output of a launch: event log + burst pool + cursors.  Two slots, so the host can
     // harvest launch k (copy back, order, transport layer) while launch k+1 runs.
     struct Slot {
-        same::DevEvent *d_events = nullptr; uint32_t event_cap = 0;
+        same::DevBuf<same::DevEvent> d_events;
+        uint32_t event_cap() const { return (uint32_t)d_events.size(); }
         // the log's indices ordered by state column, made on the device behind the launch (launch_event_sort)
-        uint32_t *d_sort = nullptr; size_t sort_words = 0;          // cnt [bins] | first [bins + 1] | the scan's workgroup totals
-        uint32_t *h_sort = nullptr; size_t h_sort_words = 0;        // pinned: first [bins + 1]
-        same::DevEvent *d_sorted = nullptr; uint32_t sorted_cap = 0; // the log's records in column order
+        same::DevBuf<uint32_t> d_sort;              // cnt [bins] | first [bins + 1] | the scan's workgroup totals
+        same::PinnedBuf<uint32_t> h_sort;           // first [bins + 1]
+        same::DevBuf<same::DevEvent> d_sorted;      // the log's records in column order
         uint32_t sort_bins = 0;
-        uint8_t *d_bursts = nullptr; uint32_t burst_cap = 0;
-        uint32_t *d_counters = nullptr;  // [0] n_events [1] n_bursts [2] overflow
-        uint32_t *h_counters = nullptr;  // pinned, host-mapped
-        uint32_t *h_counters_dev = nullptr;  // device view of h_counters
-        hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done = nullptr, ev_planned = nullptr;
-        hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;         // around the demodulation kernel alone (time-parallel launches bracket more with ev_start / ev_stop)
+        same::DevBuf<uint8_t> d_bursts;             // kBurstCap bytes per burst
+        uint32_t burst_cap() const { return (uint32_t)(d_bursts.size() / same::kBurstCap); }
+        same::DevBuf<uint32_t> d_counters;          // [0] n_events [1] n_bursts [2] overflow
+        same::MappedBuf<uint32_t> h_counters;       // their copy the host reads in place
+        same::Event ev_start, ev_stop, ev_done, ev_planned;
+        same::Event ev_k0, ev_k1;                   // around the demodulation kernel alone (time-parallel launches bracket more with ev_start / ev_stop)
         bool have_k = false;
         bool timed = false;               // ev_start / ev_stop were recorded for this launch (latched when it was made)
         // pinned landing buffers of the read-back, grown on demand.  A copy into pageable memory
         // is staged by the runtime (blit kernel + host memcpy per chunk) and, queued beside the
         // next launch, holds that launch up for as long as the host is busy.
-        void *h_events = nullptr; size_t h_events_bytes = 0;
-        void *h_bursts = nullptr; size_t h_bursts_bytes = 0;
+        same::PinnedBuf<void> h_events, h_bursts;
         bool in_flight = false;
         uint64_t seq = 0;                // launch order
         uint64_t end_counter = 0;        // input sample counter after this launch
@@ -246,35 +246,35 @@ struct same_batch {
         bool chunked = false;
         same::ChunkGeom geom{};
         uint64_t end_blocks = 0;
-        uint64_t *d_handover = nullptr, *h_handover = nullptr;
-        size_t handover_cap = 0;
+        same::DevBuf<uint64_t> d_handover;
+        same::PinnedBuf<uint64_t> h_handover;
         // per-channel chunk boundaries (channel-major input): device arrays of the launch, host copies for the stitch
         bool per_channel = false;
-        uint32_t *d_geom = nullptr;      // [own_start | row0 | nominal | perm] x columns, then wg_blocks
-        uint32_t *h_geom = nullptr;      // pinned: own_start | row0
-        size_t geom_cap = 0;
-        // channels re-initialised in front of this launch (same_batch_reset_channels): pinned, mapped, read by the reset kernel
-        uint32_t *h_reset = nullptr, *h_reset_dev = nullptr;
-        uint32_t reset_cap = 0;
-        // a ragged call's per-channel counts (same_batch_process_*_ragged): pinned, mapped, read in place by the ragged kernel
-        uint32_t *h_counts = nullptr, *h_counts_dev = nullptr;
-        uint32_t counts_cap = 0;
+        same::DevBuf<uint32_t> d_geom;       // [own_start | row0 | nominal | perm] x columns, then wg_blocks
+        same::PinnedBuf<uint32_t> h_geom;    // own_start | row0
+        // channels re-initialised in front of this launch (same_batch_reset_channels): read in place by the reset kernel
+        same::CoherentBuf<uint32_t> h_reset;
+        // a ragged call's per-channel counts (same_batch_process_*_ragged): read in place by the ragged kernel
+        same::CoherentBuf<uint32_t> h_counts;
         // the wake table as uploaded behind the launch after this slot's harvest (batches that ran ragged launches)
-        uint64_t *h_wake_up = nullptr;
+        same::PinnedBuf<uint64_t> h_wake_up;
         // SAME_BATCH_MESSAGES_ONLY: the launch's message log (same_transport.hip; its cursor is d_counters[3]) and its landing buffer
         bool dev_transport = false;      // this launch ran the transport layer on the device
         // (its first records land in host-mapped pinned memory, read in place; the rest in HBM, copied when there are any)
-        same::DevMessage *h_near = nullptr, *h_near_dev = nullptr; uint32_t near_cap = 0;
-        same::DevMessage *d_msgs = nullptr; uint32_t msg_cap = 0;
-        void *h_msgs = nullptr; size_t h_msgs_bytes = 0;
+        same::CoherentBuf<same::DevMessage> h_near;
+        uint32_t near_cap() const { return (uint32_t)h_near.size(); }
+        same::DevBuf<same::DevMessage> d_msgs;
+        uint32_t msg_cap() const { return (uint32_t)d_msgs.size(); }
+        same::PinnedBuf<void> h_msgs;
         // same_batch_set_audio_capture: the launch's span list and sample pool (same_capture_dev.h, same_capture.hip), their
         // cursors (device; published to the host-mapped copy by the capture kernel's epilogue) and pinned landing buffers
         bool captured = false;           // this launch ran the capture kernel
-        same::cap::Span *d_spans = nullptr; uint32_t span_cap = 0;
-        float *d_pool = nullptr;
-        same::cap::Cursors *d_cap_cur = nullptr, *h_cap_cur = nullptr, *h_cap_cur_dev = nullptr;
-        void *h_spans = nullptr; size_t h_spans_bytes = 0;
-        void *h_pool = nullptr; size_t h_pool_bytes = 0;
+        same::DevBuf<same::cap::Span> d_spans;
+        uint32_t span_cap() const { return (uint32_t)d_spans.size(); }
+        same::DevBuf<float> d_pool;
+        same::DevBuf<same::cap::Cursors> d_cap_cur;
+        same::MappedBuf<same::cap::Cursors> h_cap_cur;
+        same::PinnedBuf<void> h_spans, h_pool;
     } slot[2];
     // time-parallel mode (SAME_BATCH_TIME_PARALLEL)
     struct TimePar {
@@ -285,15 +285,15 @@ struct same_batch {
         int carved_kernel = -1;                               // ... and the kernel choice Pv's knobs were set for
         same::Params Pv{};
         same::State Sv{};
-        void *blob = nullptr;
-        void *blob_fresh = nullptr;                           // the same layout, every column a freshly built receiver: the template a launch's prologue copies
+        same::DevBuf<void> blob;
+        same::DevBuf<void> blob_fresh;                        // the same layout, every column a freshly built receiver: the template a launch's prologue copies
         size_t fresh_bytes = 0;                               // ... and how much of it a launch copies (the [rows][column] arrays; not the framer's rows)
-        same::StateArrayDesc *d_desc_in = nullptr, *d_desc_out = nullptr;   // real -> wide, wide -> real
+        same::DevBuf<same::StateArrayDesc> d_desc_in, d_desc_out;           // real -> wide, wide -> real
         uint32_t n_desc = 0;
-        uint32_t *d_final_col = nullptr;
-        float *d_energy = nullptr; size_t energy_cap = 0;   // scout scratch
-        float *d_hist = nullptr; size_t hist_cap = 0;       // squelch histories by grid position (PipeChunks::hist_scratch)
-        hipEvent_t ev_plan_prev = nullptr; bool plan_recorded = false;
+        same::DevBuf<uint32_t> d_final_col;
+        same::DevBuf<float> d_energy;                       // scout scratch
+        same::DevBuf<float> d_hist;                         // squelch histories by grid position (PipeChunks::hist_scratch)
+        same::Event ev_plan_prev; bool plan_recorded = false;
         int knob_plan_stream = 0;                            // SAME_TP_PLAN_STREAM=0: planning kernels stay on the launch stream (A/B measurements)
         int sort_mode = -1;                                  // SAME_TP_SORT: -1 choose, 0 grid order, 1 pieces sorted by length into workgroups, 2 groups of 64 paired long with short
         uint32_t last_chunks = 1;
@@ -315,12 +315,12 @@ struct same_batch {
         bool on = false;
         uint32_t window = 0;           // samples per window
         uint32_t fill = 0;             // samples of the current window that have arrived
-        void *d_buf = nullptr; size_t buf_bytes = 0;
-        hipEvent_t ev_buf = nullptr;   // behind the last operation on d_buf (a later call may come on another stream)
+        same::DevBuf<void> d_buf;
+        same::Event ev_buf;            // behind the last operation on d_buf (a later call may come on another stream)
         hipStream_t buf_stream = nullptr; bool buf_used = false;
         // behind the last operation of each of the two latest process calls that read the caller's buffer (or the batch's
         // staging / upload buffers): call k waits for call k - 2's before it returns (inv_reads_end)
-        hipEvent_t ev_read[2] = {nullptr, nullptr};
+        same::Event ev_read[2];
         uint64_t n_reads = 0;          // process calls so far; the latest one's event is ev_read[(n_reads - 1) & 1]
         hipStream_t read_stream = nullptr;
     } inv;
@@ -343,11 +343,10 @@ struct same_batch {
     int host_threads = 0;            // SAME_HOST_THREADS: harvest threads (0 = choose)
     uint32_t sym_max_channels = 1u << 30;
     // staging for host / channel-major inputs
-    void *d_stage = nullptr; size_t stage_bytes = 0;
-    void *d_stage2 = nullptr; size_t stage2_bytes = 0;
-    void *d_upload = nullptr; size_t upload_bytes = 0;      // host-buffer entry points: grow-only upload slab
-    void *d_zero = nullptr; size_t zero_bytes = 0;          // flush: grow-only slab of zeros
-    hipEvent_t ev_order = nullptr;                          // same_batch_order_after
+    same::DevBuf<void> d_stage, d_stage2;
+    same::DevBuf<void> d_upload;                            // host-buffer entry points: grow-only upload slab
+    same::DevBuf<void> d_zero;                              // flush: grow-only slab of zeros
+    same::Event ev_order;                                   // same_batch_order_after
     // kernel timing
     bool timing = false;
     bool have_timing = false;
@@ -369,7 +368,7 @@ struct same_batch {
     std::vector<same::TransportHot> thot;
     std::vector<same::TransportCold> tcold;
     same::TransportRef tr(uint32_t c) { return same::TransportRef(thot[c], tcold[c]); }
-    uint64_t *h_wake = nullptr;      // host mirror of State::wake_sample (pinned, n_channels words, zero = unarmed)
+    same::PinnedBuf<uint64_t> h_wake; // host mirror of State::wake_sample (n_channels words, zero = unarmed)
     // A ragged launch moves the device's wake-up instants itself (the ragged kernel), in stream order.  From the first one on the
     // host's re-arming of the table is stream-ordered as well (behind the launch in flight, with its shifts added), so that an
     // upload can no longer land across a ragged launch and undo its shift.
@@ -380,14 +379,14 @@ struct same_batch {
     bool messages_only = false;
     bool dev_transport = false;
     bool last_dev_transport = false; // the last process call's launches ran it there (same_batch_transport_on_device)
-    void *d_thot = nullptr, *d_tcold = nullptr;
+    same::DevBuf<void> d_thot, d_tcold;
     // per-channel resets (same_batch_reset_channels): where each half of a reset is due, the channels' counter bases
     same::ResetLedger resets;
     std::vector<uint32_t> reset_list, reset_now, reset_cols;       // scratch: the entry point's, the reset kernel's list
     // alert audio per message (same_batch_set_audio_capture)
     struct Audio {
         size_t per_launch = 0;                   // pool samples per slot; 0: capture is off
-        same::cap::Rec *d_rec = nullptr;         // per channel: the device's capture record
+        same::DevBuf<same::cap::Rec> d_rec;      // per channel: the device's capture record
         std::vector<uint8_t> open;               // per channel: a capture is open as far as the queued chunks go (END_RESET chunks)
         uint64_t flush_at = UINT64_MAX;          // batch counter where the running same_batch_flush began
         PodQueue<AudioChunk> queue;              // chunks not yet dropped: [head, size)
@@ -508,87 +507,29 @@ int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::
     const size_t per_chan_bursts = (size_t)(symbols / 160.0) + 4;   // a burst is >= 20 bytes
     size_t ecap = std::min<size_t>(per_chan_events * n_ch, 0x7fffffffu / sizeof(same::DevEvent));
     size_t bcap = std::min<size_t>(per_chan_bursts * n_ch, 0x7fffffffu / same::kBurstCap);
-    if (ecap > sl.event_cap) {
-        if (sl.d_events) HIP_TRY(hipFree(sl.d_events));
-        sl.d_events = nullptr; sl.event_cap = 0;
-        HIP_TRY(hipMalloc((void **)&sl.d_events, ecap * sizeof(same::DevEvent)));
-        sl.event_cap = (uint32_t)ecap;
-    }
-    if (bcap > sl.burst_cap) {
-        if (sl.d_bursts) HIP_TRY(hipFree(sl.d_bursts));
-        sl.d_bursts = nullptr; sl.burst_cap = 0;
-        HIP_TRY(hipMalloc((void **)&sl.d_bursts, bcap * same::kBurstCap));
-        sl.burst_cap = (uint32_t)bcap;
-    }
+    HIP_TRY(sl.d_events.ensure(ecap));
+    HIP_TRY(sl.d_bursts.ensure(bcap * same::kBurstCap));
     if (rx->dev_transport && !n_columns) {
         // a message needs a burst, except a pending one from an earlier launch and a forced end of message: two per channel more
-        const size_t mcap = std::min<size_t>(bcap + 2 * n_ch, 0x7fffffffu / sizeof(same::DevMessage));
-        if (mcap > sl.msg_cap) {
-            if (sl.d_msgs) HIP_TRY(hipFree(sl.d_msgs));
-            sl.d_msgs = nullptr; sl.msg_cap = 0;
-            HIP_TRY(hipMalloc((void **)&sl.d_msgs, mcap * sizeof(same::DevMessage)));
-            sl.msg_cap = (uint32_t)mcap;
-        }
-        if (!sl.h_near) {
-            // (a copy of a few kilobytes beside a launch that fills the machine waits for that launch: measured 2.7 ms at the
-            // 32 768-channel shard, the host spinning on it; writes into mapped memory need no copy)
-            const uint32_t want = std::max<uint32_t>(4096u, (uint32_t)(n_ch / 4u));
-            HIP_TRY(hipHostMalloc((void **)&sl.h_near, (size_t)want * sizeof(same::DevMessage), hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_near_dev, sl.h_near, 0));
-            sl.near_cap = want;
-        }
-        if (rx->audio.per_launch) {
-            // a message ends at most one span, a channel's tail or flush adds one: spans past this are lost only when the
-            // message log overflows too
-            const size_t scap = std::min<size_t>(n_ch + (size_t)sl.near_cap + sl.msg_cap, 0x7fffffffu / sizeof(same::cap::Span));
-            if (scap > sl.span_cap) {
-                if (sl.d_spans) HIP_TRY(hipFree(sl.d_spans));
-                sl.d_spans = nullptr; sl.span_cap = 0;
-                HIP_TRY(hipMalloc((void **)&sl.d_spans, scap * sizeof(same::cap::Span)));
-                sl.span_cap = (uint32_t)scap;
-            }
-        }
+        HIP_TRY(sl.d_msgs.ensure(std::min<size_t>(bcap + 2 * n_ch, 0x7fffffffu / sizeof(same::DevMessage))));
+        // (a copy of a few kilobytes beside a launch that fills the machine waits for that launch: measured 2.7 ms at the
+        // 32 768-channel shard, the host spinning on it; writes into mapped memory need no copy)
+        if (!sl.h_near) HIP_TRY(sl.h_near.ensure(std::max<uint32_t>(4096u, (uint32_t)(n_ch / 4u))));
+        // a message ends at most one span, a channel's tail or flush adds one: spans past this are lost only when the
+        // message log overflows too
+        if (rx->audio.per_launch)
+            HIP_TRY(sl.d_spans.ensure(std::min<size_t>(n_ch + (size_t)sl.near_cap() + sl.msg_cap(), 0x7fffffffu / sizeof(same::cap::Span))));
     }
-    {
-        const size_t need = 2 * n_ch + 1 + same::event_sort_extra_words((uint32_t)n_ch), need_h = n_ch + 1;
-        if (sl.event_cap > sl.sorted_cap) {
-            if (sl.d_sorted) HIP_TRY(hipFree(sl.d_sorted));
-            sl.d_sorted = nullptr; sl.sorted_cap = 0;
-            HIP_TRY(hipMalloc((void **)&sl.d_sorted, (size_t)sl.event_cap * sizeof(same::DevEvent)));
-            sl.sorted_cap = sl.event_cap;
-        }
-        if (need > sl.sort_words) {
-            if (sl.d_sort) HIP_TRY(hipFree(sl.d_sort));
-            sl.d_sort = nullptr; sl.sort_words = 0;
-            HIP_TRY(hipMalloc((void **)&sl.d_sort, need * sizeof(uint32_t)));
-            sl.sort_words = need;
-        }
-        if (need_h > sl.h_sort_words) {
-            if (sl.h_sort) HIP_TRY(hipHostFree(sl.h_sort));
-            sl.h_sort = nullptr; sl.h_sort_words = 0;
-            HIP_TRY(hipHostMalloc((void **)&sl.h_sort, need_h * sizeof(uint32_t), hipHostMallocDefault));
-            sl.h_sort_words = need_h;
-        }
-        sl.sort_bins = (uint32_t)n_ch;
-    }
-    O.events = sl.d_events; O.event_cap = sl.event_cap;
-    O.bursts = sl.d_bursts; O.burst_cap = sl.burst_cap;
+    HIP_TRY(sl.d_sorted.ensure(sl.d_events.size()));
+    HIP_TRY(sl.d_sort.ensure(2 * n_ch + 1 + same::event_sort_extra_words((uint32_t)n_ch)));
+    HIP_TRY(sl.h_sort.ensure(n_ch + 1));
+    sl.sort_bins = (uint32_t)n_ch;
+    O.events = sl.d_events; O.event_cap = sl.event_cap();
+    O.bursts = sl.d_bursts; O.burst_cap = sl.burst_cap();
     O.n_events = sl.d_counters; O.n_bursts = sl.d_counters + 1; O.overflow = sl.d_counters + 2;
     return SAME_OK;
 }
 
-int ensure_stage(void **p, size_t *have, size_t need)
-{
-    if (need <= *have) return SAME_OK;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr; *have = 0;
-    HIP_TRY(hipMalloc(p, need));
-    *have = need;
-    return SAME_OK;
-}
-
-// The relaxed-arithmetic pipeline of a launch over Pv.n_channels state columns: the symbol-paced one (36-sample steps,
-// same_kernels_sym.hip; 72-sample steps at 44.1 / 48 kHz) where it is built, else the FASTMATH build of the strict pipeline
 // the configuration as the pipeline's FASTMATH build takes it: 64-channel workgroups, the split form
 same::Params fm_params(const same::Params &P)
 {
@@ -596,18 +537,24 @@ same::Params fm_params(const same::Params &P)
     Pfm.knob_pipe_lanes = 64; Pfm.knob_pipe_share = 1; Pfm.knob_pipe_split = 1; Pfm.knob_pipe = 1;
     return Pfm;
 }
+// the configuration of `columns` state columns side by side (time-parallel launches): no device ticks, no trace; fastmath:
+// as fm_params takes it; force_pipe: the pipeline kernel whatever the column count
+same::Params wide_params(const same::Params &P, uint32_t columns, bool fastmath, bool force_pipe)
+{
+    same::Params Pv = fastmath ? fm_params(P) : P;
+    Pv.n_channels = columns; Pv.ticks = 0; Pv.trace_cap = 0;
+    if (force_pipe) Pv.knob_pipe = 1;
+    return Pv;
+}
+// The relaxed-arithmetic pipeline of a launch over Pv.n_channels state columns: the symbol-paced one (36-sample steps,
+// same_kernels_sym.hip; 72-sample steps at 44.1 / 48 kHz) where it is built, else the FASTMATH build of the strict pipeline
 uint32_t fm_block_len(const same::Params &Pv) { return same::sym_kernel_supported(Pv) ? same::sym_block_len(Pv) : same::pipe_block_len(Pv); }
 template <typename SampleT>
 hipError_t launch_fm(const same::Params &Pv, const same::State &Sv, const same::Output &O, const float4 *taps, const SampleT *x,
                      uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const same::PipeChunks &pc)
 {
-    if constexpr (sizeof(SampleT) == 4) {
-        if (same::sym_kernel_supported(Pv)) return same::launch_demod_sym(Pv, Sv, O, taps, (const float *)x, n_blocks, counter0, stream, pc);
-        return same::launch_demod_pipe(Pv, Sv, O, taps, (const float *)x, n_blocks, counter0, stream, pc, true);
-    } else {
-        if (same::sym_kernel_supported(Pv)) return same::launch_demod_sym_i16(Pv, Sv, O, taps, (const int16_t *)x, n_blocks, counter0, stream, pc);
-        return same::launch_demod_pipe_i16(Pv, Sv, O, taps, (const int16_t *)x, n_blocks, counter0, stream, pc, true);
-    }
+    if (same::sym_kernel_supported(Pv)) return same::launch_demod_sym(Pv, Sv, O, taps, x, n_blocks, counter0, stream, pc);
+    return same::launch_demod_pipe(Pv, Sv, O, taps, x, n_blocks, counter0, stream, pc, true);
 }
 
 // The host half of a reset of channel c at stream position `pos` (same_batch_reset_channels): the transport layer goes Idle and
@@ -634,19 +581,12 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
     std::vector<uint32_t> &cols = rx->reset_cols;
     rx->resets.take_device(cols);
     const uint32_t n = (uint32_t)cols.size();
-    if (n > sl.reset_cap) {
-        if (sl.h_reset) HIP_TRY(hipHostFree(sl.h_reset));
-        sl.h_reset = nullptr; sl.h_reset_dev = nullptr; sl.reset_cap = 0;
-        const uint32_t want = std::max<uint32_t>(256u, n + n / 2u);
-        HIP_TRY(hipHostMalloc((void **)&sl.h_reset, (size_t)want * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_reset_dev, sl.h_reset, 0));
-        sl.reset_cap = want;
-    }
+    if (n > sl.h_reset.size()) HIP_TRY(sl.h_reset.ensure(std::max<uint32_t>(256u, n + n / 2u)));
     std::memcpy(sl.h_reset, cols.data(), (size_t)n * sizeof(uint32_t));
-    hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset_dev, n, stream);
+    hipError_t e = same::launch_reset_columns(rx->P, rx->S, sl.h_reset.dev(), n, stream);
     // (SAME_BATCH_MESSAGES_ONLY: the transport layer lives on the device, and is reset there at the same position)
     if (e == hipSuccess && rx->dev_transport)
-        e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, sl.h_reset_dev, n, 0, stream, rx->audio.d_rec);
+        e = same::launch_transport_reset(rx->d_thot, rx->d_tcold, rx->P.n_channels, sl.h_reset.dev(), n, 0, stream, rx->audio.d_rec);
     if (e != hipSuccess) return fail(SAME_EHIP, "channel reset launch failed: %s", hipGetErrorString(e));
     return SAME_OK;
 }
@@ -671,11 +611,20 @@ void prepare_queue_append(same_batch *rx)
 }
 
 struct HarvestTimes { std::chrono::steady_clock::time_point sorted, replayed; uint32_t n_threads = 1; };
-int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, std::vector<uint32_t> &rearm, HarvestTimes &times)
+// what it reads of a launch: the slot's landing buffers, or a recorded launch's (same_debug_harvest_replay)
+struct HarvestInput {
+    const uint32_t *first;           // [columns + 1] the columns' ranges of `events`
+    same::DevEvent *events;          // each range is sorted in place
+    const uint8_t *bursts;
+    const uint64_t *handover;        // a time-parallel launch's
+    const uint32_t *geom;            // ... with per-channel boundaries: own_start | row0
+};
+int harvest_host(same_batch *rx, same_batch::Slot &sl, const HarvestInput &in, uint32_t n_events, uint32_t n_bursts, std::vector<uint32_t> &rearm,
+                 HarvestTimes &times)
 {
     const bool dbg = rx->debug;
-    const same::DevEvent *evs = static_cast<const same::DevEvent *>(sl.h_events);
-    const uint8_t *bursts = static_cast<const uint8_t *>(sl.h_bursts);
+    const same::DevEvent *evs = in.events;
+    const uint8_t *bursts = in.bursts;
     const uint32_t n_ch = rx->P.n_channels;
     const uint32_t n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;     // state columns of the launch
     // Per column the device emits in time order (a lane takes its log slots one after the other); across lanes the
@@ -684,8 +633,8 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     // a range they stand in the order the scatter's atomics landed, and the replay threads sort each range (a handful
     // of records) back into log order = time order before they walk it.
     // (slots a wavefront reserved but did not use carry kDevEventNone and were skipped there)
-    std::vector<uint32_t> first(sl.h_sort, sl.h_sort + n_bins + 1u);
-    same::DevEvent *evs_mut = static_cast<same::DevEvent *>(sl.h_events);
+    std::vector<uint32_t> first(in.first, in.first + n_bins + 1u);
+    same::DevEvent *evs_mut = in.events;
     const uint32_t n_real = first[n_bins];
     if (n_real > n_events) return fail(SAME_EHIP, "internal: event sort counted %u of %u events", n_real, n_events);
     // (what follows indexes the ordered copy directly)
@@ -693,14 +642,14 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     if (dbg && sl.chunked && sl.per_channel) {
         // how the per-channel boundaries came out: chunk lengths (own range + warm-up) and run-ons, in samples
         const same::ChunkGeom &g = sl.geom;
-        const uint32_t *own = sl.h_geom, *rows = sl.h_geom + n_bins;
+        const uint32_t *own = in.geom, *rows = in.geom + n_bins;
         double len_sum = 0, run_sum = 0; uint64_t len_max = 0, run_max = 0, n_len = 0, n_run = 0, n_inf = 0, n_late = 0;
         uint32_t worst_c = 0;
         for (uint32_t k = 0; k + 1u < g.n_chunks; ++k)
             for (uint32_t c = 0; c < n_ch; ++c) {
                 const uint64_t end = own[(size_t)(k + 1u) * n_ch + c], len = end - rows[(size_t)k * n_ch + c];
                 len_sum += (double)len; if (len > len_max) { len_max = len; worst_c = c; } ++n_len;
-                const uint64_t h = sl.h_handover[(size_t)k * n_ch + c];
+                const uint64_t h = in.handover[(size_t)k * n_ch + c];
                 if (h == same::kNoHandover) { ++n_inf; continue; }
                 const uint64_t run = h - g.counter0 > end ? h - g.counter0 - end : 0;
                 run_sum += (double)run; run_max = std::max(run_max, run); ++n_run; n_late += run > 2u * g.block_len;
@@ -792,9 +741,9 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     // the middle, or with a duplicate of the burst the previous chunk has just delivered).
     auto stitch = [&](Part &part, same_rx_event &ev, uint32_t c) {
         const same::ChunkGeom &g = sl.geom;
-        const uint64_t *hand = sl.h_handover;
+        const uint64_t *hand = in.handover;
         // per-channel boundaries: own_start[k][c] and row0[k][c] as the device planned them
-        const uint32_t *own = sl.per_channel ? sl.h_geom : nullptr, *rows = sl.per_channel ? sl.h_geom + n_bins : nullptr;
+        const uint32_t *own = sl.per_channel ? in.geom : nullptr, *rows = sl.per_channel ? in.geom + n_bins : nullptr;
         auto owner_of = [&](uint64_t h) -> uint32_t {
             if (!own) return g.owner_of(h);
             uint32_t k = 0;
@@ -965,17 +914,43 @@ int harvest_host(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32
     return SAME_OK;
 }
 
-int record_harvest(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, const char *path);
+// ---- a harvest on file (tools/host_step_probe.py --ranks N: the host half of a step without a device) ----------------
+// SAME_RECORD_HARVEST=<path>: the third harvest of a batch writes what the host half reads -- the ordered log, the columns'
+// offsets, the burst pool, hand-over instants and chunk geometry -- to <path>.
+struct HarvestFileHeader {
+    uint64_t magic;                  // "SAMEHRV1"
+    uint32_t n_channels, n_bins, n_events, n_bursts, chunked, per_channel, flags, input_rate, tp_enabled, pad;
+    same::ChunkGeom geom;
+    uint64_t end_blocks, end_counter;
+};
+constexpr uint64_t kHarvestMagic = 0x3156524845'4d4153ull;
+int record_harvest(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, const char *path)
+{
+    if (sl.seq != 3u) return SAME_OK;
+    std::FILE *f = std::fopen(path, "wb");
+    if (!f) return fail(SAME_EINVAL, "SAME_RECORD_HARVEST: cannot write %s", path);
+    const uint32_t n_ch = rx->P.n_channels, n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;
+    HarvestFileHeader h{};
+    h.magic = kHarvestMagic;
+    h.n_channels = n_ch; h.n_bins = n_bins; h.n_events = n_events; h.n_bursts = n_bursts;
+    h.chunked = sl.chunked; h.per_channel = sl.per_channel; h.flags = rx->flags; h.input_rate = rx->P.input_rate; h.tp_enabled = rx->tp.enabled;
+    h.geom = sl.geom; h.end_blocks = sl.end_blocks; h.end_counter = sl.end_counter;
+    bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1;
+    ok = ok && std::fwrite(sl.h_sort, sizeof(uint32_t), (size_t)n_bins + 1, f) == (size_t)n_bins + 1;
+    ok = ok && (!n_events || std::fwrite(sl.h_events, sizeof(same::DevEvent), n_events, f) == n_events);
+    ok = ok && (!n_bursts || std::fwrite(sl.h_bursts, same::kBurstCap, n_bursts, f) == n_bursts);
+    if (sl.chunked) {
+        ok = ok && std::fwrite(sl.h_handover, sizeof(uint64_t), n_bins, f) == n_bins;
+        if (sl.per_channel) ok = ok && std::fwrite(sl.h_geom, sizeof(uint32_t), (size_t)2 * n_bins, f) == (size_t)2 * n_bins;
+    }
+    std::fclose(f);
+    return ok ? SAME_OK : fail(SAME_EINVAL, "SAME_RECORD_HARVEST: short write to %s", path);
+}
 
 // a pinned landing buffer of at least `need` bytes
-hipError_t grow_pinned(void **p, size_t *have, size_t need)
+hipError_t grow_pinned(same::PinnedBuf<void> &b, size_t need)
 {
-    if (need <= *have) return hipSuccess;
-    if (*p) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-    const size_t want = need + need / 2 + 4096;
-    hipError_t e = hipHostMalloc(p, want, hipHostMallocDefault);
-    if (e == hipSuccess) *have = want;
-    return e;
+    return need <= b.size() ? hipSuccess : b.ensure(need + need / 2 + 4096);
 }
 
 // Before chunks are appended to the audio queue: reclaim the dropped prefix once it is at least as large as what is still queued
@@ -1024,20 +999,20 @@ int harvest_audio(same_batch *rx, same_batch::Slot &sl)
 {
     sl.captured = false;
     same_batch::Audio &A = rx->audio;
-    const same::cap::Cursors cur = *sl.h_cap_cur;
+    const same::cap::Cursors cur = *sl.h_cap_cur.get();
     if (cur.overflow) rx->overflowed = true;
-    const uint32_t n_spans = std::min(cur.n_spans, sl.span_cap);
+    const uint32_t n_spans = std::min(cur.n_spans, sl.span_cap());
     if (!n_spans) return SAME_OK;
     const size_t used = (size_t)std::min<unsigned long long>(cur.pool_used, (unsigned long long)A.per_launch);
-    HIP_TRY(grow_pinned(&sl.h_spans, &sl.h_spans_bytes, (size_t)n_spans * sizeof(same::cap::Span)));
+    HIP_TRY(grow_pinned(sl.h_spans, (size_t)n_spans * sizeof(same::cap::Span)));
     HIP_TRY(hipMemcpyAsync(sl.h_spans, sl.d_spans, (size_t)n_spans * sizeof(same::cap::Span), hipMemcpyDeviceToHost, rx->copy_stream));
     if (used) {
-        HIP_TRY(grow_pinned(&sl.h_pool, &sl.h_pool_bytes, used * sizeof(float)));
+        HIP_TRY(grow_pinned(sl.h_pool, used * sizeof(float)));
         HIP_TRY(hipMemcpyAsync(sl.h_pool, sl.d_pool, used * sizeof(float), hipMemcpyDeviceToHost, rx->copy_stream));
     }
     HIP_TRY(hipStreamSynchronize(rx->copy_stream));
-    const same::cap::Span *sp = static_cast<const same::cap::Span *>(sl.h_spans);
-    const float *pool = static_cast<const float *>(sl.h_pool);
+    const same::cap::Span *sp = static_cast<const same::cap::Span *>(sl.h_spans.get());
+    const float *pool = static_cast<const float *>(sl.h_pool.get());
     std::vector<uint32_t> order(n_spans);
     size_t n_samples = 0;
     for (uint32_t i = 0; i < n_spans; ++i) {
@@ -1071,16 +1046,16 @@ int harvest_audio(same_batch *rx, same_batch::Slot &sl)
 int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_clock::time_point t_begin,
                      std::chrono::steady_clock::time_point t_waited)
 {
-    const uint32_t n_msgs = std::min(sl.h_counters[3], sl.near_cap + sl.msg_cap);
-    const uint32_t n_near = std::min(n_msgs, sl.near_cap), n_far = n_msgs - n_near;
+    const uint32_t n_msgs = std::min(sl.h_counters[3], sl.near_cap() + sl.msg_cap());
+    const uint32_t n_near = std::min(n_msgs, sl.near_cap()), n_far = n_msgs - n_near;
     const size_t far_bytes = (size_t)n_far * sizeof(same::DevMessage);
     if (n_far) {
-        HIP_TRY(grow_pinned(&sl.h_msgs, &sl.h_msgs_bytes, far_bytes));
+        HIP_TRY(grow_pinned(sl.h_msgs, far_bytes));
         HIP_TRY(hipMemcpyAsync(sl.h_msgs, sl.d_msgs, far_bytes, hipMemcpyDeviceToHost, rx->copy_stream));
         HIP_TRY(hipStreamSynchronize(rx->copy_stream));
     }
     auto t_copied = std::chrono::steady_clock::now();
-    const same::DevMessage *far = static_cast<const same::DevMessage *>(sl.h_msgs);
+    const same::DevMessage *far = static_cast<const same::DevMessage *>(sl.h_msgs.get());
     auto rec = [&](uint32_t i) -> const same::DevMessage & { return i < n_near ? sl.h_near[i] : far[i - n_near]; };
     std::vector<uint32_t> order(n_msgs);
     size_t n_bytes = 0;
@@ -1141,7 +1116,7 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
 int upload_wake_ordered(same_batch *rx, same_batch::Slot &sl)
 {
     const uint32_t C = rx->P.n_channels;
-    if (!sl.h_wake_up) HIP_TRY(hipHostMalloc((void **)&sl.h_wake_up, (size_t)C * sizeof(uint64_t), hipHostMallocDefault));
+    HIP_TRY(sl.h_wake_up.ensure(C));
     same_batch::Slot &other = rx->slot[(&sl - rx->slot) ^ 1];
     const int oi = (int)(&other - rx->slot);
     for (uint32_t c = 0; c < C; ++c) {
@@ -1175,17 +1150,17 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
         rx->have_timing = true;
     }
     auto t_waited = std::chrono::steady_clock::now();
-    const uint32_t n_events = std::min(sl.h_counters[0], sl.event_cap);
+    const uint32_t n_events = std::min(sl.h_counters[0], sl.event_cap());
     if (dbg)
         std::fprintf(stderr, "[same] harvest: %u device events (%u bursts), cap %u/%u\n", sl.h_counters[0],
-                     sl.h_counters[1], sl.event_cap, sl.burst_cap);
-    const uint32_t n_bursts = std::min(sl.h_counters[1], sl.burst_cap);
+                     sl.h_counters[1], sl.event_cap(), sl.burst_cap());
+    const uint32_t n_bursts = std::min(sl.h_counters[1], sl.burst_cap());
     if (sl.h_counters[2] & (3u | same::kMessageLogOverflow)) rx->overflowed = true;
     if (sl.h_counters[2] & 4u) rx->kernel_fault = true;
     if (sl.dev_transport) return harvest_messages(rx, sl, t_begin, t_waited);
     const size_t ev_bytes = (size_t)n_events * sizeof(same::DevEvent), bu_bytes = (size_t)n_bursts * same::kBurstCap;
-    HIP_TRY(grow_pinned(&sl.h_events, &sl.h_events_bytes, ev_bytes));
-    HIP_TRY(grow_pinned(&sl.h_bursts, &sl.h_bursts_bytes, bu_bytes));
+    HIP_TRY(grow_pinned(sl.h_events, ev_bytes));
+    HIP_TRY(grow_pinned(sl.h_bursts, bu_bytes));
     // the event log first: it is what the sort below needs, and the sort runs while the burst pool (the larger copy) and
     // the chunk geometry are still on their way
     const uint32_t n_ch = rx->P.n_channels;
@@ -1207,7 +1182,9 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     if (!rx->record_path.empty()) { const int rrc = record_harvest(rx, sl, n_events, n_bursts, rx->record_path.c_str()); if (rrc != SAME_OK) return rrc; }
     std::vector<uint32_t> rearm;     // channels whose forced-EOM instant changed
     HarvestTimes times;
-    int rc = harvest_host(rx, sl, n_events, n_bursts, rearm, times);
+    const HarvestInput in{sl.h_sort, static_cast<same::DevEvent *>(sl.h_events.get()), static_cast<const uint8_t *>(sl.h_bursts.get()),
+                          sl.h_handover, sl.h_geom};
+    int rc = harvest_host(rx, sl, in, n_events, n_bursts, rearm, times);
     if (rc) return rc;
     // a ragged launch's counter shifts are due now that its own events are replayed: the channels' armed forced-EOM instants
     // move with them (and are re-armed), then the queued records' counter bases
@@ -1234,7 +1211,7 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
         // one upload of the whole wake table (a device word the kernel already cleared is
         // re-armed at worst to an instant in the past: one harmless extra poll)
         if (!rx->h_wake) {
-            HIP_TRY(hipHostMalloc((void **)&rx->h_wake, (size_t)rx->P.n_channels * sizeof(uint64_t), hipHostMallocDefault));
+            HIP_TRY(rx->h_wake.ensure(rx->P.n_channels));
             std::memset(rx->h_wake, 0, (size_t)rx->P.n_channels * sizeof(uint64_t));
         }
         for (uint32_t c : rearm) rx->h_wake[c] = rx->tr(c).force_eom_at();
@@ -1269,41 +1246,6 @@ int harvest(same_batch *rx)
         if (rc) return rc;
     }
     return SAME_OK;
-}
-
-int harvest(same_batch *rx);
-
-// ---- a harvest on file (tools/host_step_probe.py --ranks N: the host half of a step without a device) ----------------
-// SAME_RECORD_HARVEST=<path>: the third harvest of a batch writes what the host half reads -- the ordered log, the columns'
-// offsets, the burst pool, hand-over instants and chunk geometry -- to <path>.
-struct HarvestFileHeader {
-    uint64_t magic;                  // "SAMEHRV1"
-    uint32_t n_channels, n_bins, n_events, n_bursts, chunked, per_channel, flags, input_rate, tp_enabled, pad;
-    same::ChunkGeom geom;
-    uint64_t end_blocks, end_counter;
-};
-constexpr uint64_t kHarvestMagic = 0x3156524845'4d4153ull;
-int record_harvest(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, const char *path)
-{
-    if (sl.seq != 3u) return SAME_OK;
-    std::FILE *f = std::fopen(path, "wb");
-    if (!f) return fail(SAME_EINVAL, "SAME_RECORD_HARVEST: cannot write %s", path);
-    const uint32_t n_ch = rx->P.n_channels, n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;
-    HarvestFileHeader h{};
-    h.magic = kHarvestMagic;
-    h.n_channels = n_ch; h.n_bins = n_bins; h.n_events = n_events; h.n_bursts = n_bursts;
-    h.chunked = sl.chunked; h.per_channel = sl.per_channel; h.flags = rx->flags; h.input_rate = rx->P.input_rate; h.tp_enabled = rx->tp.enabled;
-    h.geom = sl.geom; h.end_blocks = sl.end_blocks; h.end_counter = sl.end_counter;
-    bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1;
-    ok = ok && std::fwrite(sl.h_sort, sizeof(uint32_t), (size_t)n_bins + 1, f) == (size_t)n_bins + 1;
-    ok = ok && (!n_events || std::fwrite(sl.h_events, sizeof(same::DevEvent), n_events, f) == n_events);
-    ok = ok && (!n_bursts || std::fwrite(sl.h_bursts, same::kBurstCap, n_bursts, f) == n_bursts);
-    if (sl.chunked) {
-        ok = ok && std::fwrite(sl.h_handover, sizeof(uint64_t), n_bins, f) == n_bins;
-        if (sl.per_channel) ok = ok && std::fwrite(sl.h_geom, sizeof(uint32_t), (size_t)2 * n_bins, f) == (size_t)2 * n_bins;
-    }
-    std::fclose(f);
-    return ok ? SAME_OK : fail(SAME_EINVAL, "SAME_RECORD_HARVEST: short write to %s", path);
 }
 
 // How a call of n samples is cut into time-parallel chunks: fills geom / pc and returns the number of
@@ -1354,15 +1296,12 @@ uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::Pipe
         return 1;
     }
     if (C % 16u != 0u || C > 16384u) return 1;
-    same::Params Pv = rx->P;
-    Pv.ticks = 0; Pv.trace_cap = 0;
-    if (pipe_fm) { Pv.knob_pipe_lanes = 64; Pv.knob_pipe_share = 1; Pv.knob_pipe_split = 1; Pv.knob_pipe = 1; }
     // state columns the pipeline takes at full speed: 32 768 at 22.05 kHz (two workgroups per CU), 16 384 at
     // 44.1 / 48 kHz (their window ring leaves room for one)
     // (column_cap 65 536: the channel-major path, whose workgroups are composed of pieces of similar length and may come
     // in two rounds)
     const uint32_t k_cap = (rx->P.ntaps == 42u ? column_cap : 16384u) / C;
-    if (column_cap > 32768u) Pv.knob_pipe = 1;           // the pipeline kernel whatever the column count
+    same::Params Pv = wide_params(rx->P, C, pipe_fm, column_cap > 32768u);      // (beyond 32 768: the pipeline kernel whatever the column count)
     uint32_t k_max = tp.max_chunks ? std::min(tp.max_chunks, k_cap) : k_cap;
     for (uint32_t K = k_max; K >= 2u; --K) {
         Pv.n_channels = K * C;
@@ -1377,13 +1316,8 @@ uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::Pipe
 // the hand-over records of a time-parallel launch: one per state column, device + pinned host copy
 int ensure_handover(same_batch::Slot &sl, uint32_t columns)
 {
-    if (sl.handover_cap >= columns) return SAME_OK;
-    if (sl.d_handover) HIP_TRY(hipFree(sl.d_handover));
-    if (sl.h_handover) HIP_TRY(hipHostFree(sl.h_handover));
-    sl.d_handover = nullptr; sl.h_handover = nullptr; sl.handover_cap = 0;
-    HIP_TRY(hipMalloc((void **)&sl.d_handover, (size_t)columns * sizeof(uint64_t)));
-    HIP_TRY(hipHostMalloc((void **)&sl.h_handover, (size_t)columns * sizeof(uint64_t), hipHostMallocDefault));
-    sl.handover_cap = columns;
+    HIP_TRY(sl.d_handover.ensure(columns));
+    HIP_TRY(sl.h_handover.ensure(columns));
     return SAME_OK;
 }
 
@@ -1395,41 +1329,36 @@ int ensure_wide_state(same_batch *rx, uint32_t columns)
     int rc = harvest(rx);                    // nothing in flight may still use the old layout
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    tp.Pv = rx->P;
-    tp.Pv.n_channels = columns;
-    tp.Pv.ticks = 0; tp.Pv.trace_cap = 0;
-    if (columns > 32768u) tp.Pv.knob_pipe = 1;
-    if (tp.kernel == same_batch::TimePar::kPipeRelaxed) { tp.Pv.knob_pipe_lanes = 64; tp.Pv.knob_pipe_share = 1; tp.Pv.knob_pipe_split = 1; tp.Pv.knob_pipe = 1; }
+    tp.Pv = wide_params(rx->P, columns, tp.kernel == same_batch::TimePar::kPipeRelaxed, columns > 32768u);
     if (columns > tp.cap_columns) {
-        if (tp.blob) HIP_TRY(hipFree(tp.blob));
-        if (tp.blob_fresh) HIP_TRY(hipFree(tp.blob_fresh));
-        tp.blob = nullptr; tp.blob_fresh = nullptr; tp.cap_columns = 0;
+        // (both go before either comes back: the two are the batch's largest allocations)
+        tp.cap_columns = 0;
+        HIP_TRY(tp.blob.reset());
+        HIP_TRY(tp.blob_fresh.reset());
         const size_t bytes = carve_state(tp.Pv, nullptr, tp.Sv);
-        HIP_TRY(hipMalloc(&tp.blob, bytes));
+        HIP_TRY(tp.blob.ensure(bytes));
         HIP_TRY(hipMemset(tp.blob, 0, bytes));
-        HIP_TRY(hipMalloc(&tp.blob_fresh, bytes));
+        HIP_TRY(tp.blob_fresh.ensure(bytes));
         tp.cap_columns = columns;
     }
-    const size_t blob_bytes = carve_state(tp.Pv, (char *)tp.blob, tp.Sv);
+    const size_t blob_bytes = carve_state(tp.Pv, (char *)tp.blob.get(), tp.Sv);
     {
         // The template of a launch's fresh state columns (launch_tp_prologue): this layout with SameReceiver::from's state in
         // every column (receiver.rs:539-558), made once per layout by the kernel that used to run over the columns of every launch
         same::State Sf{};
-        carve_state(tp.Pv, (char *)tp.blob_fresh, Sf);
+        carve_state(tp.Pv, (char *)tp.blob_fresh.get(), Sf);
         HIP_TRY(hipMemset(tp.blob_fresh, 0, blob_bytes));
         HIP_TRY(same::launch_init_state(tp.Pv, Sf, 0, nullptr, 0));
         HIP_TRY(hipDeviceSynchronize());
-        tp.fresh_bytes = (size_t)(reinterpret_cast<char *>(tp.Sv.fr_msg) - reinterpret_cast<char *>(tp.blob));      // (carved in 256-byte steps)
+        tp.fresh_bytes = (size_t)(reinterpret_cast<char *>(tp.Sv.fr_msg) - static_cast<char *>(tp.blob.get()));      // (carved in 256-byte steps)
     }
     std::vector<same::StateArrayDesc> in, out;
     list_state_arrays(rx->P, rx->S, tp.Sv, in);
     list_state_arrays(rx->P, tp.Sv, rx->S, out);
     tp.n_desc = (uint32_t)in.size();
-    if (!tp.d_desc_in) {
-        HIP_TRY(hipMalloc((void **)&tp.d_desc_in, in.size() * sizeof(same::StateArrayDesc)));
-        HIP_TRY(hipMalloc((void **)&tp.d_desc_out, out.size() * sizeof(same::StateArrayDesc)));
-        HIP_TRY(hipMalloc((void **)&tp.d_final_col, (size_t)rx->P.n_channels * sizeof(uint32_t)));
-    }
+    HIP_TRY(tp.d_desc_in.ensure(in.size()));
+    HIP_TRY(tp.d_desc_out.ensure(out.size()));
+    HIP_TRY(tp.d_final_col.ensure(rx->P.n_channels));
     HIP_TRY(hipMemcpy(tp.d_desc_in, in.data(), in.size() * sizeof(same::StateArrayDesc), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(tp.d_desc_out, out.data(), out.size() * sizeof(same::StateArrayDesc), hipMemcpyHostToDevice));
     tp.carved_columns = columns;
@@ -1445,6 +1374,161 @@ struct Ragged {
     uint32_t row_off = 0;
 };
 
+// One launch of a ragged call: the call row of its first row, and how many of its rows every channel consumes
+struct RaggedLaunch {
+    uint32_t row0 = 0;
+    size_t n_lock = 0;
+};
+
+// ---- The pieces every launch is made of.  process_time_major_launches and process_channel_major_native queue them in this order:
+// begin_launch, [tp_reserve, tp_start], the demodulation kernels, [tp_hand_back], [a sub-block tail], end_launch; what lies
+// between them -- the choice of kernel, the ragged remainder, the planning kernels and their stream -- is the caller's. ----
+
+// The begin of a launch into `sl`: the slot's previous launch is collected (its buffers are about to be reused), the stream is
+// ordered behind the launch before this one, and the channel resets asked for since then go in front
+int begin_launch(same_batch *rx, same_batch::Slot &sl, const same_batch::Slot &prev, hipStream_t stream)
+{
+    int rc = harvest_slot(rx, sl);
+    if (rc) return rc;
+    // a launch continues the state the previous one leaves: on another stream than that one, wait for it
+    if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
+    return launch_pending_resets(rx, sl, stream);
+}
+
+// kernel timing is latched per launch: ev_start goes in front of the launch's first kernel
+int begin_timing(same_batch *rx, same_batch::Slot &sl, hipStream_t stream)
+{
+    sl.timed = rx->timing;
+    if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_start, stream));
+    return SAME_OK;
+}
+
+// A time-parallel launch of n samples as `columns` state columns: the wide state, the output and the
+// hand-over records it needs, before anything is queued
+int tp_reserve(same_batch *rx, same_batch::Slot &sl, uint32_t columns, size_t n, const same::PipeChunks &pc, uint32_t block_len, same::Output &O)
+{
+    int rc = ensure_wide_state(rx, columns);
+    if (rc) return rc;
+    rc = ensure_output(rx, sl, std::min<size_t>(n, 3 * (size_t)pc.nominal_blocks * block_len + 65536), O, columns);
+    if (rc) return rc;
+    return ensure_handover(sl, columns);
+}
+
+// ... and its start on the stream: fresh receivers in every column (with the hand-over records, the event sort's bins and the
+// launch cursors: one kernel, launch_tp_prologue), then the channels' own state into chunk 0's columns.
+// *sort_bins_empty: the prologue kernel has emptied the event sort's bins
+int tp_start(same_batch *rx, same_batch::Slot &sl, uint32_t columns, const char *layout, hipStream_t stream, bool *sort_bins_empty)
+{
+    same_batch::TimePar &tp = rx->tp;
+    const uint32_t C = rx->P.n_channels;
+    *sort_bins_empty = false;
+    if (tp.knob_prologue >= 0) {
+        HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
+        *sort_bins_empty = sl.sort_bins == columns;
+    } else {
+        // (SAME_TP_PROLOGUE=0, A/B measurements: the launches' start as rounds 2-5 made it)
+        HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters.dev(), 0, stream));
+        HIP_TRY(same::launch_init_state(tp.Pv, tp.Sv, 0, stream, C));
+        HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
+    }
+    if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (%s), start-up: %s\n", columns, layout,
+                                tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
+    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
+    return SAME_OK;
+}
+
+// The state hand-back of a time-parallel launch: the channel's state afterwards is that of the chunk which ran to the end of
+// the input (own_start: the per-channel boundaries of a channel-major launch, [n_chunks][channels]; null: the uniform cut)
+int tp_hand_back(same_batch *rx, same_batch::Slot &sl, const same::ChunkGeom &geom, const uint32_t *own_start, hipStream_t stream)
+{
+    same_batch::TimePar &tp = rx->tp;
+    const uint32_t C = rx->P.n_channels;
+    if (own_start) HIP_TRY(same::launch_chunk_final_column_pc(sl.d_handover, own_start, C, geom.n_chunks, rx->counter, tp.d_final_col, stream));
+    else HIP_TRY(same::launch_chunk_final_column(sl.d_handover, C, geom, tp.d_final_col, stream));
+    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_out, tp.n_desc, geom.n_chunks * C, C, tp.d_final_col, C, stream));
+    return SAME_OK;
+}
+
+// What the block kernels leave of a launch (less than a block; every row where the configuration has no block kernel): the
+// any-configuration kernel on the channels' own state, over n time-major rows
+template <typename SampleT>
+int demod_tail(same_batch *rx, const same::Output &O, const SampleT *rows, size_t n, uint64_t counter0, hipStream_t stream)
+{
+    const hipError_t e = same::launch_demod(rx->P, rx->S, O, rx->d_taps, rows, (uint32_t)n, counter0, stream);
+    if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
+    return SAME_OK;
+}
+// ... over the [channels][r] corner at `corner` of a channel-major input (row pitch `pitch`), transposed to rows first
+int demod_tail_corner(same_batch *rx, const same::Output &O, const float *corner, size_t pitch, size_t r, uint64_t counter0, hipStream_t stream)
+{
+    const uint32_t C = rx->P.n_channels;
+    HIP_TRY(rx->d_stage.ensure(r * C * sizeof(float)));
+    HIP_TRY(rx->d_stage2.ensure(r * C * sizeof(float)));
+    float *staged = static_cast<float *>(rx->d_stage.get()), *rows = static_cast<float *>(rx->d_stage2.get());
+    HIP_TRY(hipMemcpy2DAsync(staged, r * sizeof(float), corner, pitch * sizeof(float), r * sizeof(float), C, hipMemcpyDeviceToDevice, stream));
+    const hipError_t e = same::launch_transpose(staged, rows, C, (uint32_t)r, stream);
+    if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
+    return demod_tail(rx, O, rows, r, counter0, stream);
+}
+
+// The end of a launch of n samples: the stop event, the event sort, the transport layer and the audio capture on the device
+// where the launch has them (rows: its time-major input, which the capture kernel reads; a channel-major launch has none),
+// the cursors published, the done event, the slot's and the batch's books, and -- while this launch runs -- the harvest of
+// the previous one
+template <typename SampleT>
+int end_launch(same_batch *rx, same_batch::Slot &sl, same_batch::Slot &prev, hipStream_t stream, const SampleT *rows, size_t n,
+               bool sort_bins_empty, const RaggedLaunch *rl = nullptr)
+{
+    if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
+    HIP_TRY(same::launch_event_sort(sl.d_events, sl.d_counters, sl.event_cap(), sl.sort_bins, sl.d_sort, sl.d_sort + sl.sort_bins,
+                                    sl.d_sorted, stream, sort_bins_empty));
+    // SAME_BATCH_MESSAGES_ONLY: the transport layer over the ordered log, a lane per channel, on the launch's stream (the next
+    // launch, which reads the forced-EOM instants it arms, is ordered behind it)
+    sl.dev_transport = rx->dev_transport && !sl.chunked;
+    rx->last_dev_transport = sl.dev_transport;
+    if (sl.dev_transport) {
+        same::TransportLaunch T{};
+        T.n_channels = rx->P.n_channels; T.input_rate = rx->P.input_rate;
+        T.first = sl.d_sort + sl.sort_bins; T.sorted = sl.d_sorted; T.counters = sl.d_counters;
+        T.bursts = sl.d_bursts; T.burst_cap = sl.burst_cap();
+        T.hot = rx->d_thot; T.cold = rx->d_tcold; T.wake_sample = rx->S.wake_sample;
+        T.near = sl.h_near.dev(); T.near_cap = sl.near_cap();
+        T.log = sl.d_msgs; T.log_cap = sl.msg_cap(); T.log_cursor = sl.d_counters + 3; T.overflow = sl.d_counters + 2;
+        // same_batch_set_audio_capture: the lanes list the spans of open messages, the capture kernel copies them out of the
+        // input behind it -- before the launch's done event, which every later reuse of the input waits for
+        sl.captured = rx->audio.per_launch != 0;
+        if (sl.captured) {
+            same::cap::Launch &K = T.cap;
+            const uint64_t fa = rx->audio.flush_at;
+            K.start = rx->counter; K.n_rows = (uint32_t)n;
+            K.flush_row = fa >= rx->counter + n ? same::cap::kNoFlush : (uint32_t)(fa > rx->counter ? fa - rx->counter : 0);
+            K.rec = rx->audio.d_rec; K.spans = sl.d_spans; K.span_cap = sl.span_cap();
+            K.n_spans = &sl.d_cap_cur->n_spans; K.pool_used = &sl.d_cap_cur->pool_used; K.pool_cap = rx->audio.per_launch;
+            K.overflow = &sl.d_cap_cur->overflow;
+        }
+        if (rl && rl->n_lock < n)
+            HIP_TRY(same::launch_transport_ragged(T, sl.h_counts.dev(), rl->row0, (uint32_t)n, stream));
+        else
+            HIP_TRY(same::launch_transport(T, stream));
+        if (sl.captured) {
+            const hipError_t e = same::launch_capture(sl.d_spans, sl.d_cap_cur, sl.span_cap(), sl.d_pool, rx->audio.per_launch, rows,
+                                                      rx->P.n_channels, (uint32_t)n, sl.h_cap_cur.dev(), stream);
+            if (e != hipSuccess) return fail(SAME_EHIP, "capture kernel launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters.dev(), 1, stream));
+    HIP_TRY(hipEventRecord(sl.ev_done, stream));
+    sl.in_flight = true;
+    sl.seq = ++rx->launch_seq;
+    rx->last_stream = stream;
+    // a ragged launch: the channels that consumed fewer than n rows lag the batch by that much more from here on
+    if (rl) rx->resets.shift(rx->ragged_by.data(), rx->counter + n, (int)(&sl - rx->slot));
+    rx->counter += n;
+    sl.end_counter = rx->counter;
+    // while this launch runs, bring in the previous one
+    return harvest_slot(rx, prev);
+}
+
 template <typename SampleT>
 int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_samples, hipStream_t stream, const Ragged *rg = nullptr)
 {
@@ -1456,11 +1540,7 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         const size_t n = std::min(kMaxChunk, n_samples - done);
         same_batch::Slot &sl = rx->slot[rx->launch_seq & 1];
         same_batch::Slot &prev = rx->slot[(rx->launch_seq & 1) ^ 1];
-        int rc = harvest_slot(rx, sl);          // its buffers are about to be reused
-        if (rc) return rc;
-        // a launch continues the state the previous one leaves: on another stream than that one, wait for it
-        if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
-        rc = launch_pending_resets(rx, sl, stream);
+        int rc = begin_launch(rx, sl, prev, stream);
         if (rc) return rc;
         // a ragged call: rows [0, n_lock) of this launch are every channel's (the common prefix: the lockstep kernels below),
         // rows [n_lock, n) only some channels' (the ragged kernel, behind them in the same launch)
@@ -1469,13 +1549,7 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             const size_t row0 = (size_t)rg->row_off + done;
             n_lock = rg->m > row0 ? std::min<size_t>(rg->m - row0, n) : 0;
             const uint32_t C = rx->P.n_channels;
-            if (C > sl.counts_cap) {
-                if (sl.h_counts) HIP_TRY(hipHostFree(sl.h_counts));
-                sl.h_counts = nullptr; sl.h_counts_dev = nullptr; sl.counts_cap = 0;
-                HIP_TRY(hipHostMalloc((void **)&sl.h_counts, (size_t)C * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-                HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_counts_dev, sl.h_counts, 0));
-                sl.counts_cap = C;
-            }
+            HIP_TRY(sl.h_counts.ensure(C));
             // (the slot's previous launch, the last reader of this buffer, has been harvested above)
             std::memcpy(sl.h_counts, rg->counts, (size_t)C * sizeof(uint32_t));
             rx->ragged_by.resize(C);
@@ -1494,58 +1568,28 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         if (n_chunks > 1u) {
             // Time-parallel launch: every channel as n_chunks state columns side by side.
             const uint32_t C = rx->P.n_channels, columns = n_chunks * C;
-            rc = ensure_wide_state(rx, columns);
-            if (rc) return rc;
             const size_t fbk = geom.block_len;
-            const size_t per_column = std::min<size_t>(n, 3 * (size_t)pc.nominal_blocks * fbk + 65536);
-            rc = ensure_output(rx, sl, per_column, O, columns);
-            if (rc) return rc;
-            rc = ensure_handover(sl, columns);
+            rc = tp_reserve(rx, sl, columns, n, pc, geom.block_len, O);
             if (rc) return rc;
             pc.handover = sl.d_handover;
             same_batch::TimePar &tp = rx->tp;
-            sl.timed = rx->timing; if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_start, stream));
-            // fresh receivers in every column (with the hand-over records, the event sort's bins and the launch cursors: one
-            // kernel), then the channels' own state into chunk 0's columns
-            if (tp.knob_prologue >= 0) {
-                HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
-                sort_bins_empty = sl.sort_bins == columns;
-            } else {
-                // (SAME_TP_PROLOGUE=0, A/B measurements: the launches' start as rounds 2-5 made it)
-                HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 0, stream));
-                HIP_TRY(same::launch_init_state(tp.Pv, tp.Sv, 0, stream, C));
-                HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
-            }
-            if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (time-major), start-up: %s\n", columns,
-                                        tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
-            HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
+            rc = begin_timing(rx, sl, stream);
+            if (rc) return rc;
+            rc = tp_start(rx, sl, columns, "time-major", stream, &sort_bins_empty);
+            if (rc) return rc;
             const SampleT *xp = d_x + done * C;
             const uint32_t total_blocks = (uint32_t)(n / fbk);
-            hipError_t e;
-            if (tp.kernel == same_batch::TimePar::kPipeRelaxed)
-                e = launch_fm(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc);
-            else if constexpr (sizeof(SampleT) == 4)
-                e = tp.kernel == same_batch::TimePar::kWaveRelaxed
-                        ? same::launch_demod_relaxed(tp.Pv, tp.Sv, O, rx->d_taps, (const float *)xp, total_blocks, rx->counter, stream, pc)
-                        : same::launch_demod_pipe(tp.Pv, tp.Sv, O, rx->d_taps, (const float *)xp, total_blocks, rx->counter, stream, pc, false);
-            else
-                e = tp.kernel == same_batch::TimePar::kWaveRelaxed
-                        ? same::launch_demod_relaxed_i16(tp.Pv, tp.Sv, O, rx->d_taps, (const int16_t *)xp, total_blocks, rx->counter, stream, pc)
-                        : same::launch_demod_pipe_i16(tp.Pv, tp.Sv, O, rx->d_taps, (const int16_t *)xp, total_blocks, rx->counter, stream, pc, false);
+            const hipError_t e = tp.kernel == same_batch::TimePar::kPipeRelaxed
+                                     ? launch_fm(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc)
+                                     : (tp.kernel == same_batch::TimePar::kWaveRelaxed
+                                            ? same::launch_demod_relaxed(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc)
+                                            : same::launch_demod_pipe(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc, false));
             if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
-            // the channel's state afterwards is that of the chunk which ran to the end of the input
-            HIP_TRY(same::launch_chunk_final_column(sl.d_handover, C, geom, tp.d_final_col, stream));
-            HIP_TRY(same::launch_copy_state_columns(tp.d_desc_out, tp.n_desc, columns, C, tp.d_final_col, C, stream));
+            rc = tp_hand_back(rx, sl, geom, nullptr, stream);
+            if (rc) return rc;
+            // less than a block is left: on the channels' own state
             const size_t n_whole = (size_t)total_blocks * fbk;
-            if (n_whole < n) {
-                // less than a block is left: the any-configuration kernel, on the channels' own state
-                const SampleT *xr = xp + n_whole * C;
-                if constexpr (sizeof(SampleT) == 4)
-                    e = same::launch_demod(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n - n_whole), rx->counter + n_whole, stream);
-                else
-                    e = same::launch_demod_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n - n_whole), rx->counter + n_whole, stream);
-                if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
-            }
+            if (n_whole < n && (rc = demod_tail(rx, O, xp + n_whole * C, n - n_whole, rx->counter + n_whole, stream)) != SAME_OK) return rc;
             sl.chunked = true; sl.per_channel = false;
             sl.geom = geom;
             sl.end_blocks = rx->counter + n_whole;
@@ -1554,8 +1598,9 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         sl.chunked = false; sl.per_channel = false;
         rc = ensure_output(rx, sl, n, O);
         if (rc) return rc;
-        HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 0, stream));
-        sl.timed = rx->timing; if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_start, stream));
+        HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters.dev(), 0, stream));
+        rc = begin_timing(rx, sl, stream);
+        if (rc) return rc;
         const SampleT *xp = d_x + done * rx->P.n_channels;
         hipError_t e = hipSuccess;
         // whole blocks (16 or 18 samples) go to the latency-optimised kernel when the
@@ -1588,98 +1633,26 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             rx->last_fm_sym = same::sym_kernel_supported(Pfm);
             if (e != hipSuccess) return fail(SAME_EHIP, "relaxed pipeline launch failed: %s", hipGetErrorString(e));
         } else if (n_fast && plain_wave) {
-            if constexpr (sizeof(SampleT) == 4)
-                e = same::launch_demod_relaxed(rx->P, rx->S, O, rx->d_taps, (const float *)xp, (uint32_t)(n_fast / fb), rx->counter, stream);
-            else
-                e = same::launch_demod_relaxed_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xp, (uint32_t)(n_fast / fb), rx->counter, stream);
+            e = same::launch_demod_relaxed(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream);
             if (e != hipSuccess) return fail(SAME_EHIP, "relaxed demod kernel launch failed: %s", hipGetErrorString(e));
         } else if (n_fast) {
-            const bool pipe = same::pipe_kernel_selected(rx->P);
-            if constexpr (sizeof(SampleT) == 4)
-                e = pipe ? same::launch_demod_pipe(rx->P, rx->S, O, rx->d_taps, (const float *)xp, (uint32_t)(n_fast / fb), rx->counter, stream)
-                         : same::launch_demod_fast(rx->P, rx->S, O, rx->d_taps, (const float *)xp, (uint32_t)(n_fast / fb), rx->counter, stream);
-            else
-                e = pipe ? same::launch_demod_pipe_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xp, (uint32_t)(n_fast / fb), rx->counter, stream)
-                         : same::launch_demod_fast_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xp, (uint32_t)(n_fast / fb), rx->counter, stream);
+            e = same::pipe_kernel_selected(rx->P) ? same::launch_demod_pipe(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream)
+                                                  : same::launch_demod_fast(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream);
             if (e != hipSuccess) return fail(SAME_EHIP, "fast demod kernel launch failed: %s", hipGetErrorString(e));
         }
-        if (n_fast < n_lock) {
-            const SampleT *xr = xp + n_fast * rx->P.n_channels;
-            if constexpr (sizeof(SampleT) == 4)
-                e = same::launch_demod(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n_lock - n_fast), rx->counter + n_fast, stream);
-            else
-                e = same::launch_demod_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n_lock - n_fast), rx->counter + n_fast, stream);
-            if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
-        }
+        if (n_fast < n_lock &&
+            (rc = demod_tail(rx, O, xp + n_fast * rx->P.n_channels, n_lock - n_fast, rx->counter + n_fast, stream)) != SAME_OK) return rc;
         if (n_lock < n) {
             // the ragged remainder: each lane its own count, the state left canonical at the launch's end
-            const SampleT *xr = xp + n_lock * rx->P.n_channels;
-            const uint32_t sub = (uint32_t)(rg->row_off + done + n_lock);
-            if constexpr (sizeof(SampleT) == 4)
-                e = same::launch_demod_ragged(rx->P, rx->S, O, rx->d_taps, (const float *)xr, (uint32_t)(n - n_lock), sl.h_counts_dev, sub,
-                                              rx->counter + n_lock, stream);
-            else
-                e = same::launch_demod_ragged_i16(rx->P, rx->S, O, rx->d_taps, (const int16_t *)xr, (uint32_t)(n - n_lock), sl.h_counts_dev,
-                                                  sub, rx->counter + n_lock, stream);
+            e = same::launch_demod_ragged(rx->P, rx->S, O, rx->d_taps, xp + n_lock * rx->P.n_channels, (uint32_t)(n - n_lock), sl.h_counts.dev(),
+                                          (uint32_t)(rg->row_off + done + n_lock), rx->counter + n_lock, stream);
             if (e != hipSuccess) return fail(SAME_EHIP, "ragged demod kernel launch failed: %s", hipGetErrorString(e));
         }
         }
-        if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
-        HIP_TRY(same::launch_event_sort(sl.d_events, sl.d_counters, sl.event_cap, sl.sort_bins, sl.d_sort, sl.d_sort + sl.sort_bins,
-                                        sl.d_sorted, stream, sort_bins_empty));
-        // SAME_BATCH_MESSAGES_ONLY: the transport layer over the ordered log, a lane per channel, on the launch's stream (the next
-        // launch, which reads the forced-EOM instants it arms, is ordered behind it)
-        sl.dev_transport = rx->dev_transport && !sl.chunked;
-        rx->last_dev_transport = sl.dev_transport;
-        if (sl.dev_transport) {
-            same::TransportLaunch T{};
-            T.n_channels = rx->P.n_channels; T.input_rate = rx->P.input_rate;
-            T.first = sl.d_sort + sl.sort_bins; T.sorted = sl.d_sorted; T.counters = sl.d_counters;
-            T.bursts = sl.d_bursts; T.burst_cap = sl.burst_cap;
-            T.hot = rx->d_thot; T.cold = rx->d_tcold; T.wake_sample = rx->S.wake_sample;
-            T.near = sl.h_near_dev; T.near_cap = sl.near_cap;
-            T.log = sl.d_msgs; T.log_cap = sl.msg_cap; T.log_cursor = sl.d_counters + 3; T.overflow = sl.d_counters + 2;
-            // same_batch_set_audio_capture: the lanes list the spans of open messages, the capture kernel copies them out of the
-            // input behind it -- before the launch's done event, which every later reuse of the input waits for
-            sl.captured = rx->audio.per_launch != 0;
-            if (sl.captured) {
-                same::cap::Launch &K = T.cap;
-                const uint64_t fa = rx->audio.flush_at;
-                K.start = rx->counter; K.n_rows = (uint32_t)n;
-                K.flush_row = fa >= rx->counter + n ? same::cap::kNoFlush : (uint32_t)(fa > rx->counter ? fa - rx->counter : 0);
-                K.rec = rx->audio.d_rec; K.spans = sl.d_spans; K.span_cap = sl.span_cap;
-                K.n_spans = &sl.d_cap_cur->n_spans; K.pool_used = &sl.d_cap_cur->pool_used; K.pool_cap = rx->audio.per_launch;
-                K.overflow = &sl.d_cap_cur->overflow;
-            }
-            if (rg && n_lock < n)
-                HIP_TRY(same::launch_transport_ragged(T, sl.h_counts_dev, (uint32_t)(rg->row_off + done), (uint32_t)n, stream));
-            else
-                HIP_TRY(same::launch_transport(T, stream));
-            if (sl.captured) {
-                const SampleT *xc = d_x + done * rx->P.n_channels;
-                hipError_t e;
-                if constexpr (sizeof(SampleT) == 4)
-                    e = same::launch_capture(sl.d_spans, sl.d_cap_cur, sl.span_cap, sl.d_pool, rx->audio.per_launch, (const float *)xc,
-                                             rx->P.n_channels, (uint32_t)n, sl.h_cap_cur_dev, stream);
-                else
-                    e = same::launch_capture_i16(sl.d_spans, sl.d_cap_cur, sl.span_cap, sl.d_pool, rx->audio.per_launch, (const int16_t *)xc,
-                                                 rx->P.n_channels, (uint32_t)n, sl.h_cap_cur_dev, stream);
-                if (e != hipSuccess) return fail(SAME_EHIP, "capture kernel launch failed: %s", hipGetErrorString(e));
-            }
-        }
-        HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 1, stream));
-        HIP_TRY(hipEventRecord(sl.ev_done, stream));
-        sl.in_flight = true;
-        sl.seq = ++rx->launch_seq;
-        rx->last_stream = stream;
-        // a ragged launch: the channels that consumed fewer than n rows lag the batch by that much more from here on
-        if (rg) rx->resets.shift(rx->ragged_by.data(), rx->counter + n, (int)(&sl - rx->slot));
-        rx->counter += n;
-        sl.end_counter = rx->counter;
-        done += n;
-        // while this launch runs, bring in the previous one
-        rc = harvest_slot(rx, prev);
+        const RaggedLaunch rl{rg ? (uint32_t)(rg->row_off + done) : 0u, n_lock};
+        rc = end_launch(rx, sl, prev, stream, d_x + done * rx->P.n_channels, n, sort_bins_empty, rg ? &rl : nullptr);
         if (rc) return rc;
+        done += n;
     }
     return SAME_OK;
 }
@@ -1707,9 +1680,21 @@ static int inv_buffer_wait(same_batch *rx, hipStream_t stream)
 static int inv_buffer_done(same_batch *rx, hipStream_t stream)
 {
     same_batch::Windowed &iv = rx->inv;
-    if (!iv.ev_buf) HIP_TRY(hipEventCreateWithFlags(&iv.ev_buf, hipEventDisableTiming));
+    HIP_TRY(iv.ev_buf.ensure());
     HIP_TRY(hipEventRecord(iv.ev_buf, stream));
     iv.buf_stream = stream; iv.buf_used = true;
+    return SAME_OK;
+}
+// n samples into the waiting buffer, as f32
+static int inv_copy(const float *d_x, float *dst, size_t n, hipStream_t stream)
+{
+    HIP_TRY(hipMemcpyAsync(dst, d_x, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    return SAME_OK;
+}
+static int inv_copy(const int16_t *d_x, float *dst, size_t n, hipStream_t stream)
+{
+    const hipError_t e = same::launch_cast_i16_f32(d_x, dst, n, stream);
+    if (e != hipSuccess) return fail(SAME_EHIP, "cast launch failed: %s", hipGetErrorString(e));
     return SAME_OK;
 }
 template <typename SampleT>
@@ -1718,17 +1703,11 @@ static int inv_append(same_batch *rx, const SampleT *d_x, size_t n, hipStream_t 
     // n samples (rows of n_channels) behind the ones already waiting
     same_batch::Windowed &iv = rx->inv;
     const size_t C = rx->P.n_channels;
-    int rc = ensure_stage(&iv.d_buf, &iv.buf_bytes, (size_t)iv.window * C * sizeof(float));
+    HIP_TRY(iv.d_buf.ensure((size_t)iv.window * C * sizeof(float)));
+    int rc = inv_buffer_wait(rx, stream);
     if (rc) return rc;
-    rc = inv_buffer_wait(rx, stream);
+    rc = inv_copy(d_x, static_cast<float *>(iv.d_buf.get()) + (size_t)iv.fill * C, n * C, stream);
     if (rc) return rc;
-    float *dst = static_cast<float *>(iv.d_buf) + (size_t)iv.fill * C;
-    if constexpr (sizeof(SampleT) == 4) {
-        HIP_TRY(hipMemcpyAsync(dst, d_x, n * C * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    } else {
-        hipError_t e = same::launch_cast_i16_f32((const int16_t *)d_x, dst, n * C, stream);
-        if (e != hipSuccess) return fail(SAME_EHIP, "cast launch failed: %s", hipGetErrorString(e));
-    }
     iv.fill += (uint32_t)n;
     return inv_buffer_done(rx, stream);
 }
@@ -1741,7 +1720,7 @@ static int inv_launch_waiting(same_batch *rx, hipStream_t stream)
     if (rc) return rc;
     const uint32_t n = iv.fill;
     iv.fill = 0;
-    rc = process_time_major_launches<float>(rx, static_cast<const float *>(iv.d_buf), n, stream);
+    rc = process_time_major_launches<float>(rx, static_cast<const float *>(iv.d_buf.get()), n, stream);
     if (rc) return rc;
     return inv_buffer_done(rx, stream);
 }
@@ -1760,8 +1739,8 @@ static int inv_reads_begin(same_batch *rx, hipStream_t stream)
 static int inv_reads_end(same_batch *rx, hipStream_t stream)
 {
     same_batch::Windowed &iv = rx->inv;
-    hipEvent_t &ev = iv.ev_read[iv.n_reads & 1];
-    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    same::Event &ev = iv.ev_read[iv.n_reads & 1];
+    if (!ev) HIP_TRY(ev.ensure());
     else HIP_TRY(hipEventSynchronize(ev));           // call k - 2's reads: its buffer may be reused once this call returns
     HIP_TRY(hipEventRecord(ev, stream));
     iv.read_stream = stream;
@@ -1833,9 +1812,7 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     if (n_chunks < 2u) return 0;
     const uint32_t C = rx->P.n_channels, columns = n_chunks * C, fb = geom.block_len;
     const bool wave = tp.kernel == same_batch::TimePar::kWaveRelaxed;
-    same::Params Pv = rx->P;
-    Pv.n_channels = columns; Pv.ticks = 0; Pv.trace_cap = 0; Pv.knob_pipe = 1;
-    if (tp.kernel == same_batch::TimePar::kPipeRelaxed) { Pv.knob_pipe_lanes = 64; Pv.knob_pipe_share = 1; Pv.knob_pipe_split = 1; }
+    const same::Params Pv = wide_params(rx->P, columns, tp.kernel == same_batch::TimePar::kPipeRelaxed, true);
     // 16-byte loads from every lane's stream (the scout's too: 16-byte aligned base and pitch; the relaxed kernel reads
     // 8 bytes at a time from even rows), full 64-column workgroups.  What is left of the call behind its last whole block
     // (less than a block) goes through the any-configuration kernel on the channels' own state afterwards.
@@ -1845,27 +1822,13 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     if (wave ? fb % 2 != 0 : (fb % 4 != 0 || same::pipe_workgroup_channels(Pv) != (uint32_t)same::kWave)) return 0;
     same_batch::Slot &sl = rx->slot[rx->launch_seq & 1];
     same_batch::Slot &prev = rx->slot[(rx->launch_seq & 1) ^ 1];
-    int rc = harvest_slot(rx, sl);
-    if (rc) return rc;
-    // a launch continues the state the previous one leaves: on another stream than that one, wait for it
-    if (prev.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, prev.ev_done, 0));
-    rc = launch_pending_resets(rx, sl, stream);
-    if (rc) return rc;
-    rc = ensure_wide_state(rx, columns);
+    int rc = begin_launch(rx, sl, prev, stream);
     if (rc) return rc;
     same::Output O{};
-    rc = ensure_output(rx, sl, std::min<size_t>(n, 3 * (size_t)pc.nominal_blocks * fb + 65536), O, columns);
+    rc = tp_reserve(rx, sl, columns, n, pc, fb, O);
     if (rc) return rc;
-    rc = ensure_handover(sl, columns);
-    if (rc) return rc;
-    if (sl.geom_cap < columns) {
-        if (sl.d_geom) HIP_TRY(hipFree(sl.d_geom));
-        if (sl.h_geom) HIP_TRY(hipHostFree(sl.h_geom));
-        sl.d_geom = nullptr; sl.h_geom = nullptr; sl.geom_cap = 0;
-        HIP_TRY(hipMalloc((void **)&sl.d_geom, ((size_t)5 * columns + 3 * (columns / same::kWave)) * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void **)&sl.h_geom, (size_t)2 * columns * sizeof(uint32_t), hipHostMallocDefault));
-        sl.geom_cap = columns;
-    }
+    HIP_TRY(sl.d_geom.ensure((size_t)5 * columns + 3 * (columns / same::kWave)));
+    HIP_TRY(sl.h_geom.ensure((size_t)2 * columns));
     same::TpPlan plan{};
     plan.channels = C; plan.n_chunks = n_chunks; plan.block_len = fb;
     // Warm-up: a per-channel boundary lies in silence, so all a fresh receiver needs before the next burst begins is a
@@ -1877,13 +1840,7 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     }
     plan.whole_samples = (uint32_t)n; plan.in_samples = n_call;
     plan.scout_blocks = (uint32_t)(n / same::tp_scout_block());
-    const size_t e_need = (size_t)C * plan.scout_blocks;
-    if (tp.energy_cap < e_need) {
-        if (tp.d_energy) HIP_TRY(hipFree(tp.d_energy));
-        tp.d_energy = nullptr; tp.energy_cap = 0;
-        HIP_TRY(hipMalloc((void **)&tp.d_energy, e_need * sizeof(float)));
-        tp.energy_cap = e_need;
-    }
+    HIP_TRY(tp.d_energy.ensure((size_t)C * plan.scout_blocks));
     uint32_t *d_own = sl.d_geom, *d_row0 = sl.d_geom + columns, *d_nom = sl.d_geom + 2 * (size_t)columns,
              *d_perm = sl.d_geom + 3 * (size_t)columns, *d_wg = sl.d_geom + 4 * (size_t)columns,
              *d_wg2 = d_wg + columns / same::kWave, *d_perm2 = d_wg2 + 2 * (columns / same::kWave);      // (d_wg2: [2][workgroups])
@@ -1896,7 +1853,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     // way the bench and a stream step: 1.695 -> 1.732 (the shorter tail hides less of the next call's planning) -- not the default.
     const bool pair_groups = tp.sort_mode == 2 && tp.kernel == same_batch::TimePar::kPipeRelaxed && same::sym_kernel_supported(tp.Pv);
     const int sort_mode = pair_groups ? 0 : (tp.sort_mode >= 0 ? (tp.sort_mode ? 1 : 0) : (columns > 32768u ? 1 : 0));
-    sl.timed = rx->timing; if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_start, stream));
+    rc = begin_timing(rx, sl, stream);
+    if (rc) return rc;
     // (sorted: the workgroups once more, longest first whatever their group -- those that wait for a free CU are then the short ones)
     const bool lpt = sort_mode != 0 || pair_groups;
     // On the library's own stream the planning kernels go to the plan stream: they need the input (ordered by
@@ -1910,7 +1868,7 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     if (tp.plan_recorded) HIP_TRY(hipStreamWaitEvent(ps, tp.ev_plan_prev, 0));
     HIP_TRY(same::launch_tp_plan(d_x, plan, tp.d_energy, d_own, d_row0, d_nom, d_perm, d_wg, sort_mode != 0, ps,
                                  lpt ? d_perm2 : nullptr, lpt ? d_wg2 : nullptr, pair_groups));
-    if (!tp.ev_plan_prev) HIP_TRY(hipEventCreateWithFlags(&tp.ev_plan_prev, hipEventDisableTiming));
+    HIP_TRY(tp.ev_plan_prev.ensure());
     HIP_TRY(hipEventRecord(tp.ev_plan_prev, ps));
     tp.plan_recorded = true;
     if (side) {
@@ -1918,33 +1876,15 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
         HIP_TRY(hipStreamWaitEvent(stream, sl.ev_planned, 0));
     }
     if (lpt) { d_perm = d_perm2; d_wg = d_wg2; }
-    // fresh receivers in every column (with the hand-over records, the event sort's bins and the launch cursors: one kernel,
-    // launch_tp_prologue), then the channels' own state into chunk 0's columns
     bool sort_bins_empty = false;
-    if (tp.knob_prologue >= 0) {
-        HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
-        sort_bins_empty = sl.sort_bins == columns;
-    } else {
-        // (SAME_TP_PROLOGUE=0, A/B measurements: the launches' start as rounds 2-5 made it)
-        HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 0, stream));
-        HIP_TRY(same::launch_init_state(tp.Pv, tp.Sv, 0, stream, C));
-        HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
-    }
-    if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (channel-major), start-up: %s\n", columns,
-                                tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
-    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
+    rc = tp_start(rx, sl, columns, "channel-major", stream, &sort_bins_empty);
+    if (rc) return rc;
     pc.handover = sl.d_handover;
     pc.col_row0 = d_row0; pc.col_nominal = d_nom; pc.wg_blocks = d_wg; pc.col_perm = (sort_mode != 0 || pair_groups) ? d_perm : nullptr;
     pc.in_samples = n_call; pc.whole_samples = (uint32_t)n;
     pc.hist_scratch = nullptr;
     if (pc.col_perm && tp.kernel == same_batch::TimePar::kPipeRelaxed && same::sym_kernel_supported(tp.Pv)) {
-        const size_t h_need = (size_t)columns * same::kSquelchHist;
-        if (tp.hist_cap < h_need) {
-            if (tp.d_hist) HIP_TRY(hipFree(tp.d_hist));
-            tp.d_hist = nullptr; tp.hist_cap = 0;
-            HIP_TRY(hipMalloc((void **)&tp.d_hist, h_need * sizeof(float)));
-            tp.hist_cap = h_need;
-        }
+        HIP_TRY(tp.d_hist.ensure((size_t)columns * same::kSquelchHist));
         pc.hist_scratch = tp.d_hist;
     }
     sl.have_k = sl.timed;
@@ -1957,38 +1897,49 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     // The channels' state afterwards: that of the chunk the hand-over chain ends in, as the host's stitch follows it --
     // the last chunk as a rule (its columns end with the input); an earlier one where a burst ran on to the end of the
     // call without a hand-over (a forced cut on a channel that is never quiet: its events are the ones that are kept).
-    HIP_TRY(same::launch_chunk_final_column_pc(sl.d_handover, d_own, C, n_chunks, rx->counter, tp.d_final_col, stream));
-    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_out, tp.n_desc, columns, C, tp.d_final_col, C, stream));
-    if (n < n_call) {
-        // less than a block is left: its [C][r] corner of the input transposed to rows, then the any-configuration kernel
-        const size_t r = n_call - n;
-        int rc2 = ensure_stage(&rx->d_stage, &rx->stage_bytes, r * C * sizeof(float));
-        if (rc2) return rc2;
-        rc2 = ensure_stage(&rx->d_stage2, &rx->stage2_bytes, r * C * sizeof(float));
-        if (rc2) return rc2;
-        HIP_TRY(hipMemcpy2DAsync(rx->d_stage, r * sizeof(float), d_x + n, n_call * sizeof(float), r * sizeof(float), C, hipMemcpyDeviceToDevice, stream));
-        hipError_t e2 = same::launch_transpose_f32((const float *)rx->d_stage, (float *)rx->d_stage2, C, (uint32_t)r, stream);
-        if (e2 == hipSuccess) e2 = same::launch_demod(rx->P, rx->S, O, rx->d_taps, (const float *)rx->d_stage2, (uint32_t)r, rx->counter + n, stream);
-        if (e2 != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e2));
-    }
+    rc = tp_hand_back(rx, sl, geom, d_own, stream);
+    if (rc) return rc;
+    // less than a block is left: its [C][r] corner of the input, on the channels' own state
+    if (n < n_call && (rc = demod_tail_corner(rx, O, d_x + n, n_call, n_call - n, rx->counter + n, stream)) != SAME_OK) return rc;
     sl.chunked = true; sl.per_channel = true;
-    sl.dev_transport = false;
-    rx->last_dev_transport = false;
     sl.geom = geom;
     sl.end_blocks = rx->counter + n;
-    if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_stop, stream));
-    HIP_TRY(same::launch_event_sort(sl.d_events, sl.d_counters, sl.event_cap, sl.sort_bins, sl.d_sort, sl.d_sort + sl.sort_bins,
-                                    sl.d_sorted, stream, sort_bins_empty));
-    HIP_TRY(same::launch_counters(sl.d_counters, sl.h_counters_dev, 1, stream));
-    HIP_TRY(hipEventRecord(sl.ev_done, stream));
-    sl.in_flight = true;
-    sl.seq = ++rx->launch_seq;
-    rx->last_stream = stream;
-    rx->counter += n_call;
-    sl.end_counter = rx->counter;
     tp.last_chunks = n_chunks; tp.last_per_channel = true;
-    rc = harvest_slot(rx, prev);          // while this launch runs, bring in the previous one
+    rc = end_launch<float>(rx, sl, prev, stream, nullptr, n_call, sort_bins_empty);
     return rc ? rc : 1;
+}
+// (the lanes' own streams are read as f32: an int16 call never qualifies)
+int process_channel_major_native(same_batch *, const int16_t *, size_t, hipStream_t) { return 0; }
+
+// A channel-major input of n_rows rows (row pitch `pitch`) as time-major launches: slabs of time are transposed through the
+// staging buffers, and launch(rows, n, t0) takes each -- n time-major rows that begin at the input's row t0
+template <typename SampleT, typename Launch>
+int transpose_in_slabs(same_batch *rx, const SampleT *d_x, size_t pitch, size_t n_rows, hipStream_t stream, Launch &&launch)
+{
+    const uint32_t C = rx->P.n_channels;
+    // (the staging buffers are the batch's own: a launch still in flight on ANOTHER stream may be reading its input out of
+    // them -- successive launches are ordered whatever their streams, so this call's first staging write waits for it)
+    for (same_batch::Slot &sl : rx->slot)
+        if (sl.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sl.ev_done, 0));
+    // (slabs of 65 520 samples: whole blocks of every kernel -- 16, 18, 20, 36 and 42 samples -- so that only the call's own
+    // tail goes through the any-configuration kernel, not one per slab)
+    const size_t slab = std::min<size_t>(n_rows, (size_t)65520);
+    HIP_TRY(rx->d_stage2.ensure(slab * C * sizeof(SampleT)));
+    for (size_t t0 = 0; t0 < n_rows; t0 += slab) {
+        const size_t n = std::min(slab, n_rows - t0);
+        // stream order keeps the previous slab's kernel ahead of this slab's staging writes
+        // the transpose kernel takes a dense [C][n] view, so the [C][n] window at t0 is copied out of the rows first
+        // (2D copy keeps this simple and is only used on the non-native layout)
+        HIP_TRY(rx->d_stage.ensure(n * C * sizeof(SampleT)));
+        SampleT *staged = static_cast<SampleT *>(rx->d_stage.get()), *rows = static_cast<SampleT *>(rx->d_stage2.get());
+        HIP_TRY(hipMemcpy2DAsync(staged, n * sizeof(SampleT), d_x + t0, pitch * sizeof(SampleT), n * sizeof(SampleT), C,
+                                 hipMemcpyDeviceToDevice, stream));
+        const hipError_t e = same::launch_transpose(staged, rows, C, (uint32_t)n, stream);
+        if (e != hipSuccess) return fail(SAME_EHIP, "transpose launch failed: %s", hipGetErrorString(e));
+        const int rc = launch(rows, n, t0);
+        if (rc) return rc;
+    }
+    return SAME_OK;
 }
 
 template <typename SampleT>
@@ -2012,42 +1963,40 @@ int process_device_on(same_batch *rx, const SampleT *d_x, size_t n_samples, uint
 {
     if (layout == SAME_LAYOUT_TIME_MAJOR) return process_time_major(rx, d_x, n_samples, stream);
     if (layout != SAME_LAYOUT_CHANNEL_MAJOR) return fail(SAME_EINVAL, "unknown layout %u", layout);
-    if constexpr (sizeof(SampleT) == 4) {
-        // (its cuts are planned per CALL: a batch that is to be independent of its calls takes the transposing path and windows)
-        const int done = rx->inv.on ? 0 : process_channel_major_native(rx, (const float *)d_x, n_samples, stream);
-        if (done) return done < 0 ? done : SAME_OK;
+    // (its cuts are planned per CALL: a batch that is to be independent of its calls takes the transposing path and windows)
+    const int done = rx->inv.on ? 0 : process_channel_major_native(rx, d_x, n_samples, stream);
+    if (done) return done < 0 ? done : SAME_OK;
+    return transpose_in_slabs(rx, d_x, n_samples, n_samples, stream,
+                              [&](const SampleT *rows, size_t n, size_t) { return process_time_major(rx, rows, n, stream); });
+}
+
+// Uploads the rows [0, n_rows) of a host buffer (channel-major: row pitch `pitch`) in slabs, so that arbitrarily long host
+// streams need bounded device memory; process(d_rows, n, t0) takes each slab -- n rows that begin at row t0, in the buffer's
+// layout with pitch n -- and every launch is collected before the next slab overwrites it
+template <typename SampleT, typename Process>
+int upload_in_slabs(same_batch *rx, const SampleT *h_x, size_t pitch, size_t n_rows, uint32_t layout, Process &&process)
+{
+    const size_t C = rx->P.n_channels;
+    const size_t slab = std::max<size_t>(1, std::min<size_t>(n_rows, ((size_t)256 << 20) / (C * sizeof(SampleT))));
+    HIP_TRY(rx->d_upload.ensure(slab * C * sizeof(SampleT)));
+    SampleT *d_in = static_cast<SampleT *>(rx->d_upload.get());
+    int rc = SAME_OK;
+    for (size_t t0 = 0; t0 < n_rows && rc == SAME_OK; t0 += slab) {
+        const size_t n = std::min(slab, n_rows - t0);
+        // (the previous slab's launch was collected below, so the buffer is free again -- unless a windowed batch only copied
+        // it into its waiting buffer, asynchronously: wait for that copy)
+        if (rx->inv.on && (rc = inv_reads_wait(rx)) != SAME_OK) break;
+        const hipError_t e = layout == SAME_LAYOUT_TIME_MAJOR
+                                 ? hipMemcpy(d_in, h_x + t0 * C, n * C * sizeof(SampleT), hipMemcpyHostToDevice)
+                                 : hipMemcpy2D(d_in, n * sizeof(SampleT), h_x + t0, pitch * sizeof(SampleT), n * sizeof(SampleT), C,
+                                               hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = fail(SAME_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
+        rc = process(d_in, n, t0);
+        if (rc == SAME_OK) rc = harvest(rx);
     }
-    // channel-major: transpose slabs of time through a staging buffer
-    // (the staging buffers are the batch's own: a launch still in flight on ANOTHER stream may be reading its input out of
-    // them -- successive launches are ordered whatever their streams, so this call's first staging write waits for it)
-    for (same_batch::Slot &sl : rx->slot)
-        if (sl.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sl.ev_done, 0));
-    // (slabs of 65 520 samples: whole blocks of every kernel -- 16, 18, 20, 36 and 42 samples -- so that only the call's own
-    // tail goes through the any-configuration kernel, not one per slab)
-    const size_t slab = std::min<size_t>(n_samples, (size_t)65520);
-    int rc = ensure_stage(&rx->d_stage2, &rx->stage2_bytes, slab * rx->P.n_channels * sizeof(SampleT));
-    if (rc) return rc;
-    for (size_t t0 = 0; t0 < n_samples; t0 += slab) {
-        const size_t n = std::min(slab, n_samples - t0);
-        // stream order keeps the previous slab's kernel ahead of this slab's staging writes
-        // rows of the source are n_samples long; transpose a [C][n] window starting at t0
-        hipError_t e;
-        // a strided window is expressed by offsetting the base and keeping the row pitch:
-        // the kernel takes a dense [C][n] view, so copy row windows first
-        // (2D copy keeps this simple and is only used on the non-native layout)
-        rc = ensure_stage(&rx->d_stage, &rx->stage_bytes, n * rx->P.n_channels * sizeof(SampleT));
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy2DAsync(rx->d_stage, n * sizeof(SampleT), d_x + t0, n_samples * sizeof(SampleT),
-                                 n * sizeof(SampleT), rx->P.n_channels, hipMemcpyDeviceToDevice, stream));
-        if constexpr (sizeof(SampleT) == 4)
-            e = same::launch_transpose_f32((const float *)rx->d_stage, (float *)rx->d_stage2, rx->P.n_channels, (uint32_t)n, stream);
-        else
-            e = same::launch_transpose_i16((const int16_t *)rx->d_stage, (int16_t *)rx->d_stage2, rx->P.n_channels, (uint32_t)n, stream);
-        if (e != hipSuccess) return fail(SAME_EHIP, "transpose launch failed: %s", hipGetErrorString(e));
-        rc = process_time_major(rx, (const SampleT *)rx->d_stage2, n, stream);
-        if (rc) return rc;
-    }
-    return SAME_OK;
+    if (rc == SAME_OK && rx->kernel_fault) return fail(SAME_EKERNEL, "a demodulation kernel's wavefronts lost step (internal hand-over timed out)");
+    if (rc == SAME_OK && rx->overflowed) return fail(SAME_EOVERFLOW, "event/burst pool overflow");
+    return rc;
 }
 
 template <typename SampleT>
@@ -2056,31 +2005,9 @@ int process_host_any(same_batch *rx, const SampleT *h_x, size_t n_samples, uint3
     if (!rx || (!h_x && n_samples)) return fail(SAME_EINVAL, "null argument");
     if (n_samples == 0) return SAME_OK;
     HIP_TRY(hipSetDevice(rx->device));
-    // upload in slabs so arbitrarily long host streams need bounded device memory
-    const size_t C = rx->P.n_channels;
-    const size_t slab = std::max<size_t>(1, std::min<size_t>(n_samples, ((size_t)256 << 20) / (C * sizeof(SampleT))));
-    int rc = ensure_stage(&rx->d_upload, &rx->upload_bytes, slab * C * sizeof(SampleT));
-    if (rc) return rc;
-    void *d_in = rx->d_upload;
-    for (size_t t0 = 0; t0 < n_samples && rc == SAME_OK; t0 += slab) {
-        const size_t n = std::min(slab, n_samples - t0);
-        hipError_t e;
-        // (the previous slab's launch was collected below, so the buffer is free again -- unless a windowed batch only copied
-        // it into its waiting buffer, asynchronously: wait for that copy)
-        if (rx->inv.on && (rc = inv_reads_wait(rx)) != SAME_OK) break;
-        if (layout == SAME_LAYOUT_TIME_MAJOR) {
-            e = hipMemcpy(d_in, h_x + t0 * C, n * C * sizeof(SampleT), hipMemcpyHostToDevice);
-        } else {
-            e = hipMemcpy2D(d_in, n * sizeof(SampleT), h_x + t0, n_samples * sizeof(SampleT),
-                            n * sizeof(SampleT), C, hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) { rc = fail(SAME_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
-        rc = process_device_any(rx, (const SampleT *)d_in, n, layout, SAME_STREAM_OWN);
-        if (rc == SAME_OK) rc = harvest(rx);
-    }
-    if (rc == SAME_OK && rx->kernel_fault) return fail(SAME_EKERNEL, "a demodulation kernel's wavefronts lost step (internal hand-over timed out)");
-    if (rc == SAME_OK && rx->overflowed) return fail(SAME_EOVERFLOW, "event/burst pool overflow");
-    return rc;
+    return upload_in_slabs(rx, h_x, n_samples, n_samples, layout, [&](const SampleT *d_in, size_t n, size_t) {
+        return process_device_any(rx, d_in, n, layout, SAME_STREAM_OWN);
+    });
 }
 
 // A ragged call (same_batch_process_*_ragged, include/same_rx.h): channel c consumes the first counts[c] of the buffer's n_rows
@@ -2110,7 +2037,6 @@ template <typename SampleT>
 int process_ragged_on(same_batch *rx, const SampleT *d_x, size_t pitch, size_t n_buf, size_t row_base, const uint32_t *counts,
                       uint32_t m, uint32_t M, uint32_t layout, hipStream_t stream)
 {
-    const uint32_t C = rx->P.n_channels;
     const size_t n_p = std::min<size_t>(M, row_base + n_buf) - row_base;
     Ragged rg; rg.counts = counts; rg.m = m;
     if (layout == SAME_LAYOUT_TIME_MAJOR) {
@@ -2120,32 +2046,11 @@ int process_ragged_on(same_batch *rx, const SampleT *d_x, size_t pitch, size_t n
         return process_time_major_launches(rx, d_x, n_p, stream, &rg);
     }
     // channel-major: every row's samples, in slabs, through the staging buffers into time-major
-    for (same_batch::Slot &sl : rx->slot)
-        if (sl.in_flight && rx->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sl.ev_done, 0));
-    const size_t slab = std::min<size_t>(n_p, (size_t)65520);
-    int rc = ensure_stage(&rx->d_stage2, &rx->stage2_bytes, slab * C * sizeof(SampleT));
-    if (rc) return rc;
-    for (size_t t0 = 0; t0 < n_p; t0 += slab) {
-        const size_t n = std::min(slab, n_p - t0);
-        rc = ensure_stage(&rx->d_stage, &rx->stage_bytes, n * C * sizeof(SampleT));
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy2DAsync(rx->d_stage, n * sizeof(SampleT), d_x + t0, pitch * sizeof(SampleT), n * sizeof(SampleT), C,
-                                 hipMemcpyDeviceToDevice, stream));
-        hipError_t e;
-        if constexpr (sizeof(SampleT) == 4)
-            e = same::launch_transpose_f32((const float *)rx->d_stage, (float *)rx->d_stage2, C, (uint32_t)n, stream);
-        else
-            e = same::launch_transpose_i16((const int16_t *)rx->d_stage, (int16_t *)rx->d_stage2, C, (uint32_t)n, stream);
-        if (e != hipSuccess) return fail(SAME_EHIP, "transpose launch failed: %s", hipGetErrorString(e));
-        if (m == M) {
-            rc = process_time_major_launches(rx, (const SampleT *)rx->d_stage2, n, stream);
-        } else {
-            rg.row_off = (uint32_t)(row_base + t0);
-            rc = process_time_major_launches(rx, (const SampleT *)rx->d_stage2, n, stream, &rg);
-        }
-        if (rc) return rc;
-    }
-    return SAME_OK;
+    return transpose_in_slabs(rx, d_x, pitch, n_p, stream, [&](const SampleT *rows, size_t n, size_t t0) {
+        if (m == M) return process_time_major_launches(rx, rows, n, stream);
+        rg.row_off = (uint32_t)(row_base + t0);
+        return process_time_major_launches(rx, rows, n, stream, &rg);
+    });
 }
 
 template <typename SampleT>
@@ -2175,26 +2080,13 @@ int process_ragged_host(same_batch *rx, const SampleT *h_x, size_t n_rows, const
     if (m == M && M == n_rows) return process_host_any(rx, h_x, n_rows, layout);
     HIP_TRY(hipSetDevice(rx->device));
     if (m != M) rx->wake_ordered = true;
-    // upload the first M rows in slabs, as process_host_any does, so that long calls need bounded device memory
-    const size_t C = rx->P.n_channels;
-    const size_t slab = std::max<size_t>(1, std::min<size_t>(M, ((size_t)256 << 20) / (C * sizeof(SampleT))));
-    rc = ensure_stage(&rx->d_upload, &rx->upload_bytes, slab * C * sizeof(SampleT));
-    if (rc) return rc;
     // (the upload buffer may still be read by a launch in flight: every launch of the batch is collected first)
     rc = harvest(rx);
-    for (size_t t0 = 0; t0 < M && rc == SAME_OK; t0 += slab) {
-        const size_t n = std::min<size_t>(slab, M - t0);
-        hipError_t e = layout == SAME_LAYOUT_TIME_MAJOR
-                           ? hipMemcpy(rx->d_upload, h_x + t0 * C, n * C * sizeof(SampleT), hipMemcpyHostToDevice)
-                           : hipMemcpy2D(rx->d_upload, n * sizeof(SampleT), h_x + t0, n_rows * sizeof(SampleT), n * sizeof(SampleT), C,
-                                         hipMemcpyHostToDevice);
-        if (e != hipSuccess) { rc = fail(SAME_EHIP, "upload failed: %s", hipGetErrorString(e)); break; }
-        rc = process_ragged_on(rx, (const SampleT *)rx->d_upload, n, n, t0, counts, m, M, layout, rx->own_stream);
-        if (rc == SAME_OK) rc = harvest(rx);
-    }
-    if (rc == SAME_OK && rx->kernel_fault) return fail(SAME_EKERNEL, "a demodulation kernel's wavefronts lost step (internal hand-over timed out)");
-    if (rc == SAME_OK && rx->overflowed) return fail(SAME_EOVERFLOW, "event/burst pool overflow");
-    return rc;
+    if (rc) return rc;
+    // the first M rows
+    return upload_in_slabs(rx, h_x, n_rows, M, layout, [&](const SampleT *d_in, size_t n, size_t t0) {
+        return process_ragged_on(rx, d_in, n, n, t0, counts, m, M, layout, rx->own_stream);
+    });
 }
 
 }  // namespace
@@ -2277,29 +2169,29 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
     TRY_OR_CLEAN(hipStreamCreateWithFlags(&rx->own_stream, hipStreamNonBlocking));
     TRY_OR_CLEAN(hipStreamCreateWithFlags(&rx->copy_stream, hipStreamNonBlocking));
     TRY_OR_CLEAN(hipStreamCreateWithFlags(&rx->plan_stream, hipStreamNonBlocking));
-    TRY_OR_CLEAN(hipEventCreateWithFlags(&rx->ev_order, hipEventDisableTiming));
+    TRY_OR_CLEAN(rx->ev_order.ensure());
     for (auto &sl : rx->slot) {
-        TRY_OR_CLEAN(hipEventCreate(&sl.ev_start));
-        TRY_OR_CLEAN(hipEventCreate(&sl.ev_stop));
-        TRY_OR_CLEAN(hipEventCreate(&sl.ev_k0));
-        TRY_OR_CLEAN(hipEventCreate(&sl.ev_k1));
-        TRY_OR_CLEAN(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
-        TRY_OR_CLEAN(hipEventCreateWithFlags(&sl.ev_planned, hipEventDisableTiming));
-        TRY_OR_CLEAN(hipMalloc((void **)&sl.d_counters, 4 * sizeof(uint32_t)));
-        TRY_OR_CLEAN(hipHostMalloc((void **)&sl.h_counters, 4 * sizeof(uint32_t), hipHostMallocMapped));
-        TRY_OR_CLEAN(hipHostGetDevicePointer((void **)&sl.h_counters_dev, sl.h_counters, 0));
+        TRY_OR_CLEAN(sl.ev_start.ensure(hipEventDefault));
+        TRY_OR_CLEAN(sl.ev_stop.ensure(hipEventDefault));
+        TRY_OR_CLEAN(sl.ev_k0.ensure(hipEventDefault));
+        TRY_OR_CLEAN(sl.ev_k1.ensure(hipEventDefault));
+        TRY_OR_CLEAN(sl.ev_done.ensure());
+        TRY_OR_CLEAN(sl.ev_planned.ensure());
+        TRY_OR_CLEAN(sl.d_counters.ensure(4));
+        TRY_OR_CLEAN(sl.h_counters.ensure(4));
     }
-    TRY_OR_CLEAN(hipMalloc((void **)&rx->d_taps, taps.size() * sizeof(float)));
+    static_assert(sizeof(float4) == 4 * sizeof(float), "the taps are uploaded in fours");
+    TRY_OR_CLEAN(rx->d_taps.ensure(taps.size() / 4));
     TRY_OR_CLEAN(hipMemcpy(rx->d_taps, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice));
-    rx->state_bytes = carve_state(rx->P, nullptr, rx->S);
-    TRY_OR_CLEAN(hipMalloc(&rx->d_state_blob, rx->state_bytes));
-    TRY_OR_CLEAN(hipMemset(rx->d_state_blob, 0, rx->state_bytes));
-    carve_state(rx->P, (char *)rx->d_state_blob, rx->S);
+    const size_t state_bytes = carve_state(rx->P, nullptr, rx->S);
+    TRY_OR_CLEAN(rx->d_state_blob.ensure(state_bytes));
+    TRY_OR_CLEAN(hipMemset(rx->d_state_blob, 0, state_bytes));
+    carve_state(rx->P, (char *)rx->d_state_blob.get(), rx->S);
     TRY_OR_CLEAN(same::launch_init_state(rx->P, rx->S, 0, rx->own_stream));
     if (rx->dev_transport) {
         // the transport layer's per-channel records in HBM: a hot line and a cold record each (same_transport_dev.h)
-        TRY_OR_CLEAN(hipMalloc(&rx->d_thot, (size_t)n_channels * same::transport_hot_bytes()));
-        TRY_OR_CLEAN(hipMalloc(&rx->d_tcold, (size_t)n_channels * same::transport_cold_bytes()));
+        TRY_OR_CLEAN(rx->d_thot.ensure((size_t)n_channels * same::transport_hot_bytes()));
+        TRY_OR_CLEAN(rx->d_tcold.ensure((size_t)n_channels * same::transport_cold_bytes()));
         TRY_OR_CLEAN(hipMemsetAsync(rx->d_tcold, 0, (size_t)n_channels * same::transport_cold_bytes(), rx->own_stream));
         TRY_OR_CLEAN(same::launch_transport_reset(rx->d_thot, rx->d_tcold, n_channels, nullptr, 0, 1, rx->own_stream));
     }
@@ -2317,65 +2209,11 @@ void same_batch_free(same_batch *rx)
     if (!rx) return;
     (void)hipSetDevice(rx->device);
     if (rx->last_stream) (void)hipStreamSynchronize(rx->last_stream);
-    if (rx->d_taps) (void)hipFree(rx->d_taps);
-    if (rx->d_state_blob) (void)hipFree(rx->d_state_blob);
-    for (auto &sl : rx->slot) {
-        if (sl.d_events) (void)hipFree(sl.d_events);
-        if (sl.d_sort) (void)hipFree(sl.d_sort);
-        if (sl.d_sorted) (void)hipFree(sl.d_sorted);
-        if (sl.h_sort) (void)hipHostFree(sl.h_sort);
-        if (sl.d_bursts) (void)hipFree(sl.d_bursts);
-        if (sl.d_counters) (void)hipFree(sl.d_counters);
-        if (sl.h_counters) (void)hipHostFree(sl.h_counters);
-        if (sl.h_events) (void)hipHostFree(sl.h_events);
-        if (sl.h_bursts) (void)hipHostFree(sl.h_bursts);
-        if (sl.ev_start) (void)hipEventDestroy(sl.ev_start);
-        if (sl.ev_stop) (void)hipEventDestroy(sl.ev_stop);
-        if (sl.ev_k0) (void)hipEventDestroy(sl.ev_k0);
-        if (sl.ev_k1) (void)hipEventDestroy(sl.ev_k1);
-        if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
-        if (sl.ev_planned) (void)hipEventDestroy(sl.ev_planned);
-        if (sl.d_handover) (void)hipFree(sl.d_handover);
-        if (sl.h_handover) (void)hipHostFree(sl.h_handover);
-        if (sl.d_geom) (void)hipFree(sl.d_geom);
-        if (sl.h_geom) (void)hipHostFree(sl.h_geom);
-        if (sl.h_reset) (void)hipHostFree(sl.h_reset);
-        if (sl.h_counts) (void)hipHostFree(sl.h_counts);
-        if (sl.h_wake_up) (void)hipHostFree(sl.h_wake_up);
-        if (sl.d_msgs) (void)hipFree(sl.d_msgs);
-        if (sl.h_near) (void)hipHostFree(sl.h_near);
-        if (sl.h_msgs) (void)hipHostFree(sl.h_msgs);
-        if (sl.d_spans) (void)hipFree(sl.d_spans);
-        if (sl.d_pool) (void)hipFree(sl.d_pool);
-        if (sl.d_cap_cur) (void)hipFree(sl.d_cap_cur);
-        if (sl.h_cap_cur) (void)hipHostFree(sl.h_cap_cur);
-        if (sl.h_spans) (void)hipHostFree(sl.h_spans);
-        if (sl.h_pool) (void)hipHostFree(sl.h_pool);
-    }
-    if (rx->audio.d_rec) (void)hipFree(rx->audio.d_rec);
-    if (rx->d_thot) (void)hipFree(rx->d_thot);
-    if (rx->d_tcold) (void)hipFree(rx->d_tcold);
-    if (rx->inv.d_buf) (void)hipFree(rx->inv.d_buf);
-    if (rx->inv.ev_buf) (void)hipEventDestroy(rx->inv.ev_buf);
-    for (hipEvent_t ev : rx->inv.ev_read) if (ev) (void)hipEventDestroy(ev);
-    if (rx->tp.blob) (void)hipFree(rx->tp.blob);
-    if (rx->tp.blob_fresh) (void)hipFree(rx->tp.blob_fresh);
-    if (rx->tp.d_desc_in) (void)hipFree(rx->tp.d_desc_in);
-    if (rx->tp.d_desc_out) (void)hipFree(rx->tp.d_desc_out);
-    if (rx->tp.d_final_col) (void)hipFree(rx->tp.d_final_col);
-    if (rx->tp.d_energy) (void)hipFree(rx->tp.d_energy);
-    if (rx->tp.d_hist) (void)hipFree(rx->tp.d_hist);
-    if (rx->tp.ev_plan_prev) (void)hipEventDestroy(rx->tp.ev_plan_prev);
-    if (rx->copy_stream) (void)hipStreamDestroy(rx->copy_stream);
-    if (rx->plan_stream) (void)hipStreamDestroy(rx->plan_stream);
-    if (rx->h_wake) (void)hipHostFree(rx->h_wake);
-    if (rx->d_stage) (void)hipFree(rx->d_stage);
-    if (rx->d_stage2) (void)hipFree(rx->d_stage2);
-    if (rx->d_upload) (void)hipFree(rx->d_upload);
-    if (rx->d_zero) (void)hipFree(rx->d_zero);
-    if (rx->ev_order) (void)hipEventDestroy(rx->ev_order);
-    if (rx->own_stream) (void)hipStreamDestroy(rx->own_stream);
+    // the members let their memory and events go; the streams last
+    const hipStream_t streams[3] = {rx->copy_stream, rx->plan_stream, rx->own_stream};
     delete rx;
+    for (hipStream_t st : streams)
+        if (st) (void)hipStreamDestroy(st);
 }
 
 int same_batch_reset(same_batch *rx)
@@ -2477,15 +2315,14 @@ int same_batch_flush(same_batch *rx)
     // four seconds of zeros per channel (receiver.rs:216-224), generated on the device
     const size_t n = (size_t)rx->P.input_rate * 4;
     const size_t slab = std::max<size_t>(1, std::min<size_t>(n, ((size_t)256 << 20) / ((size_t)rx->P.n_channels * sizeof(float))));
-    if (slab * rx->P.n_channels * sizeof(float) > rx->zero_bytes) {
-        int rc0 = ensure_stage(&rx->d_zero, &rx->zero_bytes, slab * rx->P.n_channels * sizeof(float));
-        if (rc0) return rc0;
-        HIP_TRY(hipMemset(rx->d_zero, 0, rx->zero_bytes));       // once per growth: the kernels only read it
+    if (slab * rx->P.n_channels * sizeof(float) > rx->d_zero.size()) {
+        HIP_TRY(rx->d_zero.ensure(slab * rx->P.n_channels * sizeof(float)));
+        HIP_TRY(hipMemset(rx->d_zero, 0, rx->d_zero.size()));       // once per growth: the kernels only read it
     }
     int rc = SAME_OK;
     rx->audio.flush_at = rx->counter + rx->inv.fill;      // (the zeros are never captured: a launch's rows from here on are clipped)
     for (size_t t0 = 0; t0 < n && rc == SAME_OK; t0 += slab) {
-        rc = process_device_any<float>(rx, (const float *)rx->d_zero, std::min(slab, n - t0), SAME_LAYOUT_TIME_MAJOR, SAME_STREAM_OWN);
+        rc = process_device_any<float>(rx, static_cast<const float *>(rx->d_zero.get()), std::min(slab, n - t0), SAME_LAYOUT_TIME_MAJOR, SAME_STREAM_OWN);
         if (rc == SAME_OK) rc = harvest(rx);
     }
     if (rc == SAME_OK && rx->inv.on) {
@@ -2639,13 +2476,8 @@ int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
     if (rc) return rc;
     same_batch::Audio &A = rx->audio;
     auto release = [&]() {
-        for (same_batch::Slot &sl : rx->slot) {
-            if (sl.d_pool) (void)hipFree(sl.d_pool);
-            if (sl.d_spans) (void)hipFree(sl.d_spans);
-            sl.d_pool = nullptr; sl.d_spans = nullptr; sl.span_cap = 0;
-        }
-        if (A.d_rec) (void)hipFree(A.d_rec);
-        A.d_rec = nullptr;
+        for (same_batch::Slot &sl : rx->slot) { (void)sl.d_pool.reset(); (void)sl.d_spans.reset(); }
+        (void)A.d_rec.reset();
         A.per_launch = 0;
         A.open.clear();
     };
@@ -2658,15 +2490,14 @@ int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
         return fail(SAME_ENOMEM, "audio capture: %s (%zu samples per launch)", what, samples_per_launch);
     };
     for (same_batch::Slot &sl : rx->slot) {
-        if (hipMalloc((void **)&sl.d_pool, samples_per_launch * sizeof(float)) != hipSuccess) return oom("sample pool");
+        if (sl.d_pool.ensure(samples_per_launch) != hipSuccess) return oom("sample pool");
         if (!sl.d_cap_cur) {
-            if (hipMalloc((void **)&sl.d_cap_cur, sizeof(same::cap::Cursors)) != hipSuccess) return oom("cursors");
+            if (sl.d_cap_cur.ensure(1) != hipSuccess) return oom("cursors");
             HIP_TRY(hipMemset(sl.d_cap_cur, 0, sizeof(same::cap::Cursors)));
-            if (hipHostMalloc((void **)&sl.h_cap_cur, sizeof(same::cap::Cursors), hipHostMallocMapped) != hipSuccess) return oom("cursors");
-            HIP_TRY(hipHostGetDevicePointer((void **)&sl.h_cap_cur_dev, sl.h_cap_cur, 0));
+            if (sl.h_cap_cur.ensure(1) != hipSuccess) return oom("cursors");
         }
     }
-    if (hipMalloc((void **)&A.d_rec, (size_t)rx->P.n_channels * sizeof(same::cap::Rec)) != hipSuccess) return oom("capture records");
+    if (A.d_rec.ensure(rx->P.n_channels) != hipSuccess) return oom("capture records");
     HIP_TRY(hipMemset(A.d_rec, 0, (size_t)rx->P.n_channels * sizeof(same::cap::Rec)));
     A.open.assign(rx->P.n_channels, 0);
     A.per_launch = samples_per_launch;
@@ -2864,8 +2695,7 @@ long same_debug_harvest_replay(const char *path, int threads, int reps, double *
     rx->resets.init(h.n_channels);
     same_batch::Slot &sl = rx->slot[0];
     ev = ev0; hand = hand0;
-    sl.h_sort = first.data(); sl.h_events = ev.data(); sl.h_bursts = bursts.data();
-    sl.h_handover = hand.data(); sl.h_geom = geom.data();
+    const HarvestInput in{first.data(), ev.data(), bursts.data(), hand.data(), geom.data()};
     sl.chunked = h.chunked != 0; sl.per_channel = h.per_channel != 0; sl.sort_bins = h.n_bins;
     const uint64_t span = h.end_counter - h.geom.counter0;        // (an ordinary launch: geom is zero, the span the end counter -- fine for a stride)
     const double sps = (double)h.input_rate / 520.83;
@@ -2881,14 +2711,13 @@ long same_debug_harvest_replay(const char *path, int threads, int reps, double *
         std::vector<uint32_t> rearm;
         HarvestTimes times;
         const auto t0 = std::chrono::steady_clock::now();
-        rc = harvest_host(rx, sl, h.n_events, h.n_bursts, rearm, times);
+        rc = harvest_host(rx, sl, in, h.n_events, h.n_bursts, rearm, times);
         ms_out[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         produced = (long)(rx->queue.size() - rx->queue_head);
         // the consumer's side: everything polled
         rx->queue_head = rx->queue.size();
         rx->burst_seq_head = rx->burst_seq.size();
     }
-    sl.h_sort = nullptr; sl.h_events = nullptr; sl.h_bursts = nullptr; sl.h_handover = nullptr; sl.h_geom = nullptr;
 #ifdef SAME_HOST_PROF
     { uint64_t tot = 0; for (int k = 0; k < 7; ++k) tot += g_hp[k];
       for (int k = 0; k < 7; ++k) std::fprintf(stderr, "[same prof] %-24s %8.3f Mclk per harvest (%4.1f %% of the instrumented parts)\n", g_hp_name[k], (double)g_hp[k] / reps / 1e6, tot ? 100.0 * (double)g_hp[k] / (double)tot : 0.0); }

@@ -63,8 +63,8 @@ hipError_t launch_capture(const cap::Span *spans, cap::Cursors *cur, uint32_t sp
 {
     return launch_capture_t(spans, cur, span_cap, pool, pool_cap, x, n_channels, n_rows, host, stream);
 }
-hipError_t launch_capture_i16(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
-                              const int16_t *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream)
+hipError_t launch_capture(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
+                          const int16_t *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream)
 {
     return launch_capture_t(spans, cur, span_cap, pool, pool_cap, x, n_channels, n_rows, host, stream);
 }

@@ -500,8 +500,8 @@ hipError_t launch_demod(const Params &P, const State &S, const Output &O, const 
                         const float *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream)
 { return launch_demod_t<float>(P, S, O, taps, x, n_samples, counter0, stream); }
 
-hipError_t launch_demod_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                            const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream)
+hipError_t launch_demod(const Params &P, const State &S, const Output &O, const float4 *taps,
+                        const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream)
 { return launch_demod_t<int16_t>(P, S, O, taps, x, n_samples, counter0, stream); }
 
 template <typename SampleT>
@@ -529,8 +529,8 @@ hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O,
                                uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream)
 { return launch_demod_ragged_t<float>(P, S, O, taps, x, n_rows, counts, row_sub, counter0, stream); }
 
-hipError_t launch_demod_ragged_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                   uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream)
+hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                               uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream)
 { return launch_demod_ragged_t<int16_t>(P, S, O, taps, x, n_rows, counts, row_sub, counter0, stream); }
 
 size_t demod_lds_bytes(const Params &P)
@@ -917,15 +917,15 @@ hipError_t launch_fill_u64(uint64_t *p, size_t n, uint64_t v, hipStream_t stream
     return hipGetLastError();
 }
 
-hipError_t launch_transpose_f32(const float *in, float *out, uint32_t n_channels, uint32_t n_samples,
-                                hipStream_t stream)
+hipError_t launch_transpose(const float *in, float *out, uint32_t n_channels, uint32_t n_samples,
+                            hipStream_t stream)
 {
     dim3 grid((n_samples + 63) / 64, (n_channels + 63) / 64);
     hipLaunchKernelGGL(transpose_to_time_major<float>, grid, dim3(256), 0, stream, in, out, n_channels, n_samples);
     return hipGetLastError();
 }
-hipError_t launch_transpose_i16(const int16_t *in, int16_t *out, uint32_t n_channels, uint32_t n_samples,
-                                hipStream_t stream)
+hipError_t launch_transpose(const int16_t *in, int16_t *out, uint32_t n_channels, uint32_t n_samples,
+                            hipStream_t stream)
 {
     dim3 grid((n_samples + 63) / 64, (n_channels + 63) / 64);
     hipLaunchKernelGGL(transpose_to_time_major<int16_t>, grid, dim3(256), 0, stream, in, out, n_channels, n_samples);

@@ -395,8 +395,8 @@ static hipError_t launch_fast_t(const Params &P, const State &S, const Output &O
 hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream)
 { return launch_fast_t<float>(P, S, O, taps, x, n_blocks, counter0, stream); }
-hipError_t launch_demod_fast_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                 const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream)
+hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,
+                             const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream)
 { return launch_fast_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream); }
 
 }  // namespace same

@@ -1438,8 +1438,8 @@ static hipError_t launch_pipe_t(const Params &P, const State &S, const Output &O
 hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K, bool relaxed)
 { return launch_pipe_t<float>(P, S, O, taps, x, n_blocks, counter0, stream, K, relaxed); }
-hipError_t launch_demod_pipe_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                 const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K, bool relaxed)
+hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
+                             const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K, bool relaxed)
 { return launch_pipe_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream, K, relaxed); }
 // The FASTMATH build exists for the three rates the pipeline is built for, in 64-channel workgroups (whole groups of 64
 // state columns), default or disabled equalizer, a non-negative AGC floor

@@ -855,8 +855,8 @@ static hipError_t launch_relaxed_t(const Params &P, const State &S, const Output
 hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
                                 const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_relaxed_t<float>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
-hipError_t launch_demod_relaxed_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                    const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
+hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
+                                const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_relaxed_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
 
 }  // namespace same

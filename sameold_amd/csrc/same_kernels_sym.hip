@@ -2122,26 +2122,20 @@ static hipError_t launch_sym_hi_t(const Params &P, const State &S, const Output 
 hipError_t launch_demod_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_sym_hi_t<float>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
-hipError_t launch_demod_sym_hi_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                   uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
+hipError_t launch_demod_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                               uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_sym_hi_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
 #endif
 #else
 #if defined(SYM_SPLIT_TU)
 hipError_t launch_demod_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K);
-hipError_t launch_demod_sym_hi_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                   uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K);
-static hipError_t launch_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
-                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
-{ return launch_demod_sym_hi(P, S, O, taps, x, n_blocks, counter0, stream, K); }
-static hipError_t launch_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
-{ return launch_demod_sym_hi_i16(P, S, O, taps, x, n_blocks, counter0, stream, K); }
+hipError_t launch_demod_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                               uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K);
 #else
 template <typename SampleT>
-static hipError_t launch_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const SampleT *x,
-                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
+static hipError_t launch_demod_sym_hi(const Params &P, const State &S, const Output &O, const float4 *taps, const SampleT *x,
+                                      uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_sym_hi_t<SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
 #endif
 template <typename SampleT>
@@ -2152,13 +2146,13 @@ static hipError_t launch_sym_t(const Params &P, const State &S, const Output &O,
     const bool eq = P.eq_nff == 6u && P.eq_nfb == 4u;
     if (sym_rate_nt(P) == 42u)
         return eq ? launch_sym_one<42, 6, 4, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K) : launch_sym_one<42, 1, 1, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K);
-    return launch_sym_hi(P, S, O, taps, x, n_blocks, counter0, stream, K);
+    return launch_demod_sym_hi(P, S, O, taps, x, n_blocks, counter0, stream, K);
 }
 hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
                             uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_sym_t<float>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
-hipError_t launch_demod_sym_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
+hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                            uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 { return launch_sym_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream, K); }
 #endif      // !SYM_TU_HI
 

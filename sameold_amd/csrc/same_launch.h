@@ -10,16 +10,16 @@ namespace same {
 
 hipError_t launch_demod(const Params &P, const State &S, const Output &O, const float4 *taps,
                         const float *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
-hipError_t launch_demod_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                            const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
+hipError_t launch_demod(const Params &P, const State &S, const Output &O, const float4 *taps,
+                        const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
 size_t demod_lds_bytes(const Params &P);
 // the ragged remainder of a ragged call (same_batch_process_*_ragged): rows [0, n_rows) of x, lane c consuming its first
 // min(counts[c] - row_sub, n_rows) of them (counts: device-readable, n_channels entries); leaves the state canonical at
 // counter0 + n_rows
 hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O, const float4 *taps, const float *x,
                                uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
-hipError_t launch_demod_ragged_i16(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
-                                   uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
+hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
+                               uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
 // latency-optimised kernel for the standard rates (same_kernels_fast.hip); whole blocks of
 // fast_block_len() samples, the generic kernel takes the rest of a call
 // longest block that can hold at most one TED instant for this configuration (same_config.cpp)
@@ -34,9 +34,9 @@ uint32_t pipe_block_len(const Params &P);         // samples per block of the pi
 hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                              const PipeChunks &chunks = PipeChunks{}, bool relaxed = false);
-hipError_t launch_demod_pipe_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                 const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
-                                 const PipeChunks &chunks = PipeChunks{}, bool relaxed = false);
+hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
+                             const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
+                             const PipeChunks &chunks = PipeChunks{}, bool relaxed = false);
 bool pipe_relaxed_supported(const Params &P);
 // symbol-paced pipeline (same_kernels_sym.hip): relaxed arithmetic, 22.05 kHz, 36-sample steps, whole groups of 64 state
 // columns; takes time-parallel chunks like the pipeline
@@ -45,9 +45,9 @@ uint32_t sym_block_len(const Params &P);
 hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps,
                             const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                             const PipeChunks &chunks = PipeChunks{});
-hipError_t launch_demod_sym_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
-                                const PipeChunks &chunks = PipeChunks{});
+hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps,
+                            const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
+                            const PipeChunks &chunks = PipeChunks{});
 uint32_t pipe_workgroup_channels(const Params &P);   // channels per workgroup the pipeline would use for this batch
 // relaxed-arithmetic throughput kernel (same_kernels_relaxed.hip): 22.05 kHz, one wavefront per 64 state columns,
 // whole blocks of relaxed_block_len() samples; takes time-parallel chunks like the pipeline
@@ -57,13 +57,13 @@ uint32_t relaxed_kernel_kind(const Params &P);    // 0 solo (one wavefront per 6
 hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
                                 const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                                 const PipeChunks &chunks = PipeChunks{});
-hipError_t launch_demod_relaxed_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                    const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
-                                    const PipeChunks &chunks = PipeChunks{});
+hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
+                                const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
+                                const PipeChunks &chunks = PipeChunks{});
 hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream);
-hipError_t launch_demod_fast_i16(const Params &P, const State &S, const Output &O, const float4 *taps,
-                                 const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream);
+hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,
+                             const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream);
 // zero the launch cursors (publish = 0) or copy them to host-mapped memory (publish = 1)
 hipError_t launch_counters(uint32_t *dev, uint32_t *host_mapped, int publish, hipStream_t stream);
 // the log ordered by state column: first [n_bins + 1] (exclusive offsets), sorted [cap] (the records, a column's in any
@@ -106,10 +106,10 @@ struct TpPlan {
 hipError_t launch_tp_plan(const float *x, const TpPlan &g, float *energy, uint32_t *own_start, uint32_t *row0,
                           uint32_t *nominal, uint32_t *perm, uint32_t *wg_blocks, bool sorted, hipStream_t stream,
                           uint32_t *perm_out = nullptr, uint32_t *wg_blocks_out = nullptr, bool pairs = false);
-hipError_t launch_transpose_f32(const float *in, float *out, uint32_t n_channels, uint32_t n_samples,
-                                hipStream_t stream);
-hipError_t launch_transpose_i16(const int16_t *in, int16_t *out, uint32_t n_channels, uint32_t n_samples,
-                                hipStream_t stream);
+hipError_t launch_transpose(const float *in, float *out, uint32_t n_channels, uint32_t n_samples,
+                            hipStream_t stream);
+hipError_t launch_transpose(const int16_t *in, int16_t *out, uint32_t n_channels, uint32_t n_samples,
+                            hipStream_t stream);
 
 // The transport layer on the device (same_transport.hip, SAME_BATCH_MESSAGES_ONLY): one lane per channel walks its range of
 // the launch's column-ordered log (behind launch_event_sort), runs the transport layer over it and appends the messages to
@@ -146,8 +146,8 @@ hipError_t launch_transport_reset(void *hot, void *cold, uint32_t n_channels, co
 // Then its epilogue copies the launch's cursors to `host` (host-mapped) and zeroes them.
 hipError_t launch_capture(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
                           const float *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream);
-hipError_t launch_capture_i16(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
-                              const int16_t *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream);
+hipError_t launch_capture(const cap::Span *spans, cap::Cursors *cur, uint32_t span_cap, float *pool, uint64_t pool_cap,
+                          const int16_t *x, uint32_t n_channels, uint32_t n_rows, cap::Cursors *host, hipStream_t stream);
 
 // synthetic workload (same_synth.hip)
 struct SynthParams {
