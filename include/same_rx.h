@@ -452,7 +452,8 @@ int same_batch_last_kernel_ms(same_batch *rx, float *ms);
 int same_batch_last_demod_kernel_ms(same_batch *rx, float *ms);
 /* enable/disable that timing (off by default: two event records per call) */
 void same_batch_set_kernel_timing(same_batch *rx, int enable);
-/* name of the kernel variant the last call dispatched to (static string) */
+/* name of the kernel family that ran the whole blocks of the last launch (static string); before the first call: the
+ * strict kernel of the configuration, demod_pipe_kernel, demod_fast_kernel or demod_kernel<B=..> */
 const char *same_batch_kernel_name(const same_batch *rx);
 
 /* ------------------------------------------------------------------ single receiver

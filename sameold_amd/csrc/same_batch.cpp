@@ -282,7 +282,7 @@ struct same_batch {
         uint32_t max_chunks = 0, min_own = 0, warmup = 0;     // same_batch_time_parallel_config (0 = default)
         uint32_t cap_columns = 0;                             // columns the wide state blob holds
         uint32_t carved_columns = 0;                          // columns Pv / Sv / the descriptor tables are laid out for
-        int carved_kernel = -1;                               // ... and the kernel choice Pv's knobs were set for
+        int carved_family = -1;                               // ... and the kernel family Pv's knobs were set for
         same::Params Pv{};
         same::State Sv{};
         same::DevBuf<void> blob;
@@ -298,10 +298,7 @@ struct same_batch {
         int sort_mode = -1;                                  // SAME_TP_SORT: -1 choose, 0 grid order, 1 pieces sorted by length into workgroups, 2 groups of 64 paired long with short
         uint32_t last_chunks = 1;
         bool last_per_channel = false;
-        // which kernel runs the chunks of the call being planned: the wavefront pipeline (strict, or its FASTMATH build
-        // when the batch is relaxed) or the one-wavefront relaxed kernel
-        enum Kernel { kPipe = 0, kPipeRelaxed = 1, kWaveRelaxed = 2 } kernel = kPipe;
-        int knob_kernel = 0;                                  // SAME_TP_KERNEL: 1 pipeline, 2 one-wavefront relaxed kernel, 0 choose
+        same::Family family = same::Family::kPipe;            // which kernel runs the chunks of the call being planned (plan_chunks)
         int knob_prologue = 0;                                // SAME_TP_PROLOGUE=0: init kernel, fill and cursor reset as separate launches (A/B measurements)
         std::vector<int64_t> sym_off;        // per channel: reported symbol count - the device's
         std::vector<TickSynth> synth;
@@ -331,17 +328,16 @@ struct same_batch {
     bool overflowed = false;
     std::string record_path;         // SAME_RECORD_HARVEST (measurement aid of tools/host_step_probe.py: read once per batch, like every knob)
     bool kernel_fault = false;       // counters[2] bit 2: a wavefront pipeline's bounded hand-over wait ran out (same_kernels_sym.hip)
-    bool use_fast = false;           // configuration has a latency-optimised kernel
-    bool relaxed = false;            // relaxed arithmetic in time-parallel chunks (SAME_BATCH_TIME_PARALLEL or SAME_BATCH_RELAXED)
-    bool last_plain_fm = false;      // the last ordinary launch ran the pipeline's FASTMATH build
-    bool last_plain_wave = false;    // ... the one- / two-wavefront relaxed kernel
-    bool last_fm_sym = false;        // ... or rather the symbol-paced pipeline (same_kernels_sym.hip)
-    bool relaxed_plain = false;      // ... and in ordinary launches: the one-wavefront relaxed kernel runs whole blocks (SAME_BATCH_RELAXED)
-    int knob_relaxed = 0;            // SAME_RELAXED: -1 never (time-parallel chunks keep the strict pipeline), +1 as if SAME_BATCH_RELAXED were set
-    bool force_generic = false;      // SAME_BATCH_GENERIC_KERNEL (tests compare both kernels)
+    // which kernel runs a launch (same_select.h): what the batch was created with, its arithmetic mode, the block kernel of its
+    // ordinary launches (fixed with the batch: P and the knobs never change) and the family same_batch_kernel_name reports
+    same::Request want;
+    same::Mode mode;
+    same::Choice plain;
+    same::Params Pfm{};              // fm_params(P): what the relaxed pipelines launch with
+    same::Family last_family = same::Family::kGeneric;
+    bool sym_launched = false;       // an ordinary launch has run the symbol-paced pipeline (until then its name is the FASTMATH build's, whose place it takes)
     bool debug = false;              // SAME_DEBUG: harvest statistics on stderr
     int host_threads = 0;            // SAME_HOST_THREADS: harvest threads (0 = choose)
-    uint32_t sym_max_channels = 1u << 30;
     // staging for host / channel-major inputs
     same::DevBuf<void> d_stage, d_stage2;
     same::DevBuf<void> d_upload;                            // host-buffer entry points: grow-only upload slab
@@ -484,16 +480,16 @@ void read_knobs(same_batch *rx)
 #endif
     rx->P.knob_fast_dense = tri("SAME_FAST_DENSE");
     rx->P.knob_sym = tri("SAME_SYM");
-    rx->sym_max_channels = (uint32_t)std::max(0, num("SAME_SYM_MAX", 1 << 30));     // (measurement knob: up to where an ordinary relaxed launch takes the symbol-paced pipeline; default: always)
+    rx->want.sym_max_channels = (uint32_t)std::max(0, num("SAME_SYM_MAX", 1 << 30));     // (measurement knob: up to where an ordinary relaxed launch takes the symbol-paced pipeline; default: always)
     rx->debug = std::getenv("SAME_DEBUG") != nullptr;
     { const char *e = std::getenv("SAME_RECORD_HARVEST"); rx->record_path = e ? e : ""; }
     rx->host_threads = std::max(0, num("SAME_HOST_THREADS", 0));
     rx->tp.sort_mode = num("SAME_TP_SORT", -1);
     rx->tp.knob_plan_stream = tri("SAME_TP_PLAN_STREAM");
     rx->tp.knob_prologue = tri("SAME_TP_PROLOGUE");
-    rx->knob_relaxed = tri("SAME_RELAXED");
+    rx->want.knob_relaxed = tri("SAME_RELAXED");
     { const char *e = std::getenv("SAME_RELAXED_KERNEL"); rx->P.knob_relaxed_kernel = !e ? 0 : (std::strcmp(e, "solo") == 0 ? 1 : (std::strcmp(e, "duo") == 0 ? 2 : 0)); }
-    { const char *e = std::getenv("SAME_TP_KERNEL"); rx->tp.knob_kernel = !e ? 0 : (std::strcmp(e, "wave") == 0 ? 2 : (std::strcmp(e, "pipe") == 0 ? 1 : 0)); }
+    { const char *e = std::getenv("SAME_TP_KERNEL"); rx->want.knob_tp_kernel = !e ? 0 : (std::strcmp(e, "wave") == 0 ? 2 : (std::strcmp(e, "pipe") == 0 ? 1 : 0)); }
 }
 
 int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::Output &O, size_t n_columns = 0)
@@ -530,31 +526,21 @@ int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::
     return SAME_OK;
 }
 
-// the configuration as the pipeline's FASTMATH build takes it: 64-channel workgroups, the split form
-same::Params fm_params(const same::Params &P)
-{
-    same::Params Pfm = P;
-    Pfm.knob_pipe_lanes = 64; Pfm.knob_pipe_share = 1; Pfm.knob_pipe_split = 1; Pfm.knob_pipe = 1;
-    return Pfm;
-}
-// the configuration of `columns` state columns side by side (time-parallel launches): no device ticks, no trace; fastmath:
-// as fm_params takes it; force_pipe: the pipeline kernel whatever the column count
-same::Params wide_params(const same::Params &P, uint32_t columns, bool fastmath, bool force_pipe)
-{
-    same::Params Pv = fastmath ? fm_params(P) : P;
-    Pv.n_channels = columns; Pv.ticks = 0; Pv.trace_cap = 0;
-    if (force_pipe) Pv.knob_pipe = 1;
-    return Pv;
-}
-// The relaxed-arithmetic pipeline of a launch over Pv.n_channels state columns: the symbol-paced one (36-sample steps,
-// same_kernels_sym.hip; 72-sample steps at 44.1 / 48 kHz) where it is built, else the FASTMATH build of the strict pipeline
-uint32_t fm_block_len(const same::Params &Pv) { return same::sym_kernel_supported(Pv) ? same::sym_block_len(Pv) : same::pipe_block_len(Pv); }
+// The block kernel of family `f` over n_blocks whole blocks (pc: the chunks of a time-parallel launch; the one-wavefront kernel
+// takes ordinary launches only)
 template <typename SampleT>
-hipError_t launch_fm(const same::Params &Pv, const same::State &Sv, const same::Output &O, const float4 *taps, const SampleT *x,
-                     uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const same::PipeChunks &pc)
+hipError_t launch_family(same::Family f, const same::Params &P, const same::State &S, const same::Output &O, const float4 *taps, const SampleT *x,
+                         uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const same::PipeChunks &pc = same::PipeChunks{})
 {
-    if (same::sym_kernel_supported(Pv)) return same::launch_demod_sym(Pv, Sv, O, taps, x, n_blocks, counter0, stream, pc);
-    return same::launch_demod_pipe(Pv, Sv, O, taps, x, n_blocks, counter0, stream, pc, true);
+    switch (f) {
+    case same::Family::kSym: return same::launch_demod_sym(P, S, O, taps, x, n_blocks, counter0, stream, pc);
+    case same::Family::kPipeFastmath: return same::launch_demod_pipe(P, S, O, taps, x, n_blocks, counter0, stream, pc, true);
+    case same::Family::kPipe: return same::launch_demod_pipe(P, S, O, taps, x, n_blocks, counter0, stream, pc, false);
+    case same::Family::kWaveRelaxed: return same::launch_demod_relaxed(P, S, O, taps, x, n_blocks, counter0, stream, pc);
+    case same::Family::kFast: return same::launch_demod_fast(P, S, O, taps, x, n_blocks, counter0, stream);
+    case same::Family::kGeneric: break;
+    }
+    return hipErrorInvalidValue;
 }
 
 // The host half of a reset of channel c at stream position `pos` (same_batch_reset_channels): the transport layer goes Idle and
@@ -1251,10 +1237,9 @@ int harvest(same_batch *rx)
 // How a call of n samples is cut into time-parallel chunks: fills geom / pc and returns the number of
 // chunks, or 1 when the call runs as one strict launch (mode off, configuration without a pipeline kernel,
 // call too short).
-uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::PipeChunks &pc, uint32_t column_cap = 32768u, bool channel_major = false)
+uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::PipeChunks &pc, uint32_t column_cap = same::kTpColumnCap, bool channel_major = false)
 {
     same_batch::TimePar &tp = rx->tp;
-    if (!tp.enabled || !rx->use_fast || rx->force_generic) return 1;
     const uint32_t C = rx->P.n_channels;
     const double sps = (double)rx->P.input_rate / 520.83;
     auto fill = [&](uint32_t K, uint32_t fb) -> bool {
@@ -1271,44 +1256,11 @@ uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::Pipe
         pc.handover = nullptr;
         return true;
     };
-    // Relaxed batches: the pipeline's FASTMATH build while the state columns fit the pipeline (whole 64-channel
-    // workgroups), the one-wavefront relaxed kernel beyond (SAME_TP_KERNEL=pipe / wave overrides)
-    const bool pipe_fm = rx->relaxed && tp.knob_kernel != 2 && C % same::kWave == 0u && C <= 16384u;
-    // A batch that fills the machine by itself (more than 16 384 channels, i.e. more than one workgroup per CU before any
-    // cut) gains nothing from a cut in time -- its ordinary relaxed launches run the symbol-paced pipeline at ~30 % of HBM,
-    // 262 144 state columns on the one-wavefront kernel ran at 13 % (round 3's `scaled_long`): such time-major calls are not
-    // cut, and same_batch_new has made them relaxed launches (32 768 ch x 10 s: 21 ms per call against 31.6; SAME_TP_KERNEL=wave
-    // still cuts them).  A channel-major call keeps the cut: read where it lies by the one-wavefront kernel it is 31.6 ms,
-    // transposed slab by slab first 38.6.
-    if (rx->relaxed && !pipe_fm && !channel_major && tp.knob_kernel == 0 && C % same::kWave == 0u && same::sym_kernel_supported(fm_params(rx->P))) return 1;
-    if (rx->relaxed && !pipe_fm && tp.knob_kernel != 1 && C % same::kWave == 0u && C <= 65536u && same::relaxed_kernel_supported(rx->P)) {
-        // one wavefront per 64 state columns, any number of them
-        // (up to 262 144 state columns, 16 pieces per channel unless the caller asks for more: a piece is a burst with its
-        // margins at least, so more only sit empty)
-        (void)column_cap;
-        const uint32_t k_cap = std::min(63u, 262144u / C);
-        const uint32_t k_max = tp.max_chunks ? std::min(tp.max_chunks, k_cap) : std::min(k_cap, 16u);
-        same::Params Pk = rx->P;
-        for (uint32_t K = k_max; K >= 2u; --K) {
-            Pk.n_channels = K * C;                           // (the block length follows the form the column count selects)
-            if (fill(K, same::relaxed_block_len(Pk))) { tp.kernel = same_batch::TimePar::kWaveRelaxed; return K; }
-        }
-        return 1;
-    }
-    if (C % 16u != 0u || C > 16384u) return 1;
-    // state columns the pipeline takes at full speed: 32 768 at 22.05 kHz (two workgroups per CU), 16 384 at
-    // 44.1 / 48 kHz (their window ring leaves room for one)
-    // (column_cap 65 536: the channel-major path, whose workgroups are composed of pieces of similar length and may come
-    // in two rounds)
-    const uint32_t k_cap = (rx->P.ntaps == 42u ? column_cap : 16384u) / C;
-    same::Params Pv = wide_params(rx->P, C, pipe_fm, column_cap > 32768u);      // (beyond 32 768: the pipeline kernel whatever the column count)
-    uint32_t k_max = tp.max_chunks ? std::min(tp.max_chunks, k_cap) : k_cap;
-    for (uint32_t K = k_max; K >= 2u; --K) {
-        Pv.n_channels = K * C;
-        if (!same::pipe_kernel_selected(Pv) || C % same::pipe_workgroup_channels(Pv) != 0u) continue;
-        if (pipe_fm && !same::pipe_relaxed_supported(Pv)) continue;
-        const uint32_t fb = pipe_fm ? fm_block_len(Pv) : same::pipe_block_len(Pv);
-        if (fill(K, fb)) { tp.kernel = pipe_fm ? same_batch::TimePar::kPipeRelaxed : same_batch::TimePar::kPipe; return K; }
+    // the candidates, most pieces first (same_select.h: which batches are cut, into how many pieces at most, by which kernel)
+    const same::TpRule rule = same::tp_rule(rx->P, rx->mode, rx->want, tp.max_chunks, column_cap, channel_major);
+    for (uint32_t K = rule.k_max; K >= 2u; --K) {
+        same::Choice c;
+        if (same::tp_candidate(rx->P, rule, K, c) && fill(K, c.block_len)) { tp.family = c.family; return K; }
     }
     return 1;
 }
@@ -1325,11 +1277,11 @@ int ensure_handover(same_batch::Slot &sl, uint32_t columns)
 int ensure_wide_state(same_batch *rx, uint32_t columns)
 {
     same_batch::TimePar &tp = rx->tp;
-    if (tp.carved_columns == columns && tp.carved_kernel == (int)tp.kernel) return SAME_OK;
+    if (tp.carved_columns == columns && tp.carved_family == (int)tp.family) return SAME_OK;
     int rc = harvest(rx);                    // nothing in flight may still use the old layout
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
-    tp.Pv = wide_params(rx->P, columns, tp.kernel == same_batch::TimePar::kPipeRelaxed, columns > 32768u);
+    tp.Pv = same::wide_params(rx->P, columns, same::is_fastmath(tp.family), same::tp_more_than_one_round(columns));
     if (columns > tp.cap_columns) {
         // (both go before either comes back: the two are the batch's largest allocations)
         tp.cap_columns = 0;
@@ -1362,7 +1314,7 @@ int ensure_wide_state(same_batch *rx, uint32_t columns)
     HIP_TRY(hipMemcpy(tp.d_desc_in, in.data(), in.size() * sizeof(same::StateArrayDesc), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(tp.d_desc_out, out.data(), out.size() * sizeof(same::StateArrayDesc), hipMemcpyHostToDevice));
     tp.carved_columns = columns;
-    tp.carved_kernel = (int)tp.kernel;
+    tp.carved_family = (int)tp.family;
     return SAME_OK;
 }
 
@@ -1579,11 +1531,8 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             if (rc) return rc;
             const SampleT *xp = d_x + done * C;
             const uint32_t total_blocks = (uint32_t)(n / fbk);
-            const hipError_t e = tp.kernel == same_batch::TimePar::kPipeRelaxed
-                                     ? launch_fm(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc)
-                                     : (tp.kernel == same_batch::TimePar::kWaveRelaxed
-                                            ? same::launch_demod_relaxed(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc)
-                                            : same::launch_demod_pipe(tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc, false));
+            const hipError_t e = launch_family(tp.family, tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc);
+            rx->last_family = tp.family;
             if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
             rc = tp_hand_back(rx, sl, geom, nullptr, stream);
             if (rc) return rc;
@@ -1603,43 +1552,17 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         if (rc) return rc;
         const SampleT *xp = d_x + done * rx->P.n_channels;
         hipError_t e = hipSuccess;
-        // whole blocks (16 or 18 samples) go to the latency-optimised kernel when the
-        // configuration has one; the generic kernel takes the remainder (and every other
-        // configuration)
-        // SAME_BATCH_RELAXED on an ordinary launch of whole 64-channel groups: the symbol-paced pipeline at 22.05, 44.1 and 48 kHz
-        // (any number of channels; SAME_SYM=0 puts the pipeline's FASTMATH build in its place -- round 5's relaxed kernel at 44.1 /
-        // 48 kHz, up to 32 768 channels); the one- / two-wavefront relaxed kernel takes batches that are not whole groups of 64 and
-        // whatever SAME_RELAXED_KERNEL=solo / duo sends it
-        const same::Params Pfm = fm_params(rx->P);
-        // (the symbol-paced pipeline takes any number of 64-channel workgroups: beyond two per CU they run in rounds -- and
-        // it is the faster kernel at every channel count)
-        // (at 44.1 / 48 kHz a CU holds one group of 64 columns: beyond 16 384 columns the workgroups run in rounds -- round 4 sent
-        // such batches to the strict kernels whatever the flag said)
-        const bool plain_fm = rx->relaxed_plain && rx->P.knob_relaxed_kernel == 0 && same::pipe_relaxed_supported(Pfm) &&
-                              (rx->P.n_channels <= 32768u || (rx->P.n_channels <= rx->sym_max_channels && same::sym_kernel_supported(Pfm)) ||
-                               !same::relaxed_kernel_supported(rx->P));
-        // (measured, 2 s launches back to back with the transport layer on, the way a stream is fed: 49 152 channels 4.26 ms;
-        // 98 304: 7.2 ms against the one-wavefront relaxed kernel's 12.3; 131 072: 9.45 against 15.35; 196 608: 13.95 against
-        // 24.9; 262 144: 19.5 against 29.3 -- 30 % of HBM against 18-20 %.  Round 3's figures for the one-wavefront kernel, up to
-        // 26 %, were single launches on an idle machine with the link layer only; sustained, its eight wavefronts per SIMD fall
-        // back launch by launch: tools/big_sustained.py.  SAME_RELAXED_KERNEL=solo / duo still selects it.)
-        const bool plain_wave = rx->relaxed_plain && !plain_fm && same::relaxed_kernel_supported(rx->P);
-        rx->last_plain_fm = plain_fm; rx->last_plain_wave = plain_wave;
-        const size_t fb = plain_fm ? fm_block_len(Pfm)
-                                   : (plain_wave ? same::relaxed_block_len(rx->P) : (rx->use_fast ? same::fast_block_len(rx->P) : 16));
-        size_t n_fast = (rx->use_fast && !rx->force_generic) ? (n_lock / fb) * fb : 0;
-        if (n_fast && plain_fm) {
-            e = launch_fm(Pfm, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream, same::PipeChunks{});
-            rx->last_fm_sym = same::sym_kernel_supported(Pfm);
-            if (e != hipSuccess) return fail(SAME_EHIP, "relaxed pipeline launch failed: %s", hipGetErrorString(e));
-        } else if (n_fast && plain_wave) {
-            e = same::launch_demod_relaxed(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream);
-            if (e != hipSuccess) return fail(SAME_EHIP, "relaxed demod kernel launch failed: %s", hipGetErrorString(e));
-        } else if (n_fast) {
-            e = same::pipe_kernel_selected(rx->P) ? same::launch_demod_pipe(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream)
-                                                  : same::launch_demod_fast(rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream);
-            if (e != hipSuccess) return fail(SAME_EHIP, "fast demod kernel launch failed: %s", hipGetErrorString(e));
+        // whole blocks go to the batch's block kernel (same_select.h: select_plain) where it has one; the any-configuration
+        // kernel takes the remainder (and every other configuration)
+        const same::Choice &plain = rx->plain;
+        const size_t fb = plain.block_len;
+        const size_t n_fast = fb ? (n_lock / fb) * fb : 0;
+        if (n_fast) {
+            e = launch_family(plain.family, same::is_fastmath(plain.family) ? rx->Pfm : rx->P, rx->S, O, rx->d_taps, xp, (uint32_t)(n_fast / fb), rx->counter, stream);
+            if (e != hipSuccess) return fail(SAME_EHIP, "%s launch failed: %s", same::family_name(plain.family, rx->P.block_len), hipGetErrorString(e));
+            rx->sym_launched |= plain.family == same::Family::kSym;
         }
+        rx->last_family = plain.family == same::Family::kSym && !rx->sym_launched ? same::Family::kPipeFastmath : plain.family;
         if (n_fast < n_lock &&
             (rc = demod_tail(rx, O, xp + n_fast * rx->P.n_channels, n_lock - n_fast, rx->counter + n_fast, stream)) != SAME_OK) return rc;
         if (n_lock < n) {
@@ -1794,25 +1717,12 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     if (rx->P.ntaps != 42u) return 0;
     same::ChunkGeom geom{};
     same::PipeChunks pc{};
-    // A quarter more state columns than the machine holds at once (40 960: 10 pieces per channel at 4 096 channels) unless
-    // the caller asks for a number of chunks: the launch is as long as its longest piece, a burst with its margins however
-    // many pieces there are, but with 8 pieces the planner cannot give every long burst a piece of its own (longest piece
-    // 39.9 k samples, with 10 or more 37.5 k), and beyond 10 the extra workgroups only add rounds.  Measured at 4 096
-    // channels x 10 s, pieces sorted by length into workgroups: 8 pieces 3.84 ms (unsorted 3.83), 9 3.47, 10 3.45, 11 3.70,
-    // 12 3.85, 16 4.2.
-    // With the symbol-paced pipeline (round 4): exactly the columns the machine holds at once (32 768: 8 pieces per channel at
-    // 4 096 channels, one round of workgroups in grid order).  Single launches on an idle machine favour 12 pieces (8: 2.16 ms,
-    // 10: 2.14, 12: 2.03, 16: 2.21 -- the long pieces finish with a CU to themselves), but calls back to back, the way a stream
-    // is fed, do not: 40 steps with 8 pieces 2.20 ms per step (kernel 2.05-2.08, launch to launch +-3 %), with 10: 2.38-2.42,
-    // 12: 2.41-2.48 (kernel 2.26-2.35, launch to launch 2.06-3.1), 16: 2.46 (tools/headline_steady.py).
-    const bool sym_cols = rx->relaxed && same::sym_kernel_supported(rx->P);
-    const uint32_t dflt_cols = sym_cols ? 32768u : 40960u;
-    const uint32_t want_cols = tp.max_chunks ? tp.max_chunks * rx->P.n_channels : dflt_cols;
-    const uint32_t n_chunks = plan_chunks(rx, n, geom, pc, tp.max_chunks ? (want_cols > 32768u ? 65536u : 32768u) : dflt_cols, true);
+    // (how many state columns the call may become: tp_native_column_cap, with the measurements behind it)
+    const uint32_t n_chunks = plan_chunks(rx, n, geom, pc, same::tp_native_column_cap(rx->P, rx->mode, tp.max_chunks), true);
     if (n_chunks < 2u) return 0;
     const uint32_t C = rx->P.n_channels, columns = n_chunks * C, fb = geom.block_len;
-    const bool wave = tp.kernel == same_batch::TimePar::kWaveRelaxed;
-    const same::Params Pv = wide_params(rx->P, columns, tp.kernel == same_batch::TimePar::kPipeRelaxed, true);
+    const bool wave = tp.family == same::Family::kWaveRelaxed;
+    const same::Params Pv = same::wide_params(rx->P, columns, same::is_fastmath(tp.family), true);
     // 16-byte loads from every lane's stream (the scout's too: 16-byte aligned base and pitch; the relaxed kernel reads
     // 8 bytes at a time from even rows), full 64-column workgroups.  What is left of the call behind its last whole block
     // (less than a block) goes through the any-configuration kernel on the channels' own state afterwards.
@@ -1851,8 +1761,8 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     // the symbol-paced pipeline's two-group workgroups, so that a long group runs the second part of its launch alone on its CU
     // (a step is ~12 % shorter there).  One launch by itself: demodulation kernel 1.746 -> 1.706 ms; launches back to back, the
     // way the bench and a stream step: 1.695 -> 1.732 (the shorter tail hides less of the next call's planning) -- not the default.
-    const bool pair_groups = tp.sort_mode == 2 && tp.kernel == same_batch::TimePar::kPipeRelaxed && same::sym_kernel_supported(tp.Pv);
-    const int sort_mode = pair_groups ? 0 : (tp.sort_mode >= 0 ? (tp.sort_mode ? 1 : 0) : (columns > 32768u ? 1 : 0));
+    const bool pair_groups = tp.sort_mode == 2 && tp.family == same::Family::kSym;
+    const int sort_mode = pair_groups ? 0 : (tp.sort_mode >= 0 ? (tp.sort_mode ? 1 : 0) : (same::tp_more_than_one_round(columns) ? 1 : 0));
     rc = begin_timing(rx, sl, stream);
     if (rc) return rc;
     // (sorted: the workgroups once more, longest first whatever their group -- those that wait for a free CU are then the short ones)
@@ -1883,15 +1793,14 @@ int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hip
     pc.col_row0 = d_row0; pc.col_nominal = d_nom; pc.wg_blocks = d_wg; pc.col_perm = (sort_mode != 0 || pair_groups) ? d_perm : nullptr;
     pc.in_samples = n_call; pc.whole_samples = (uint32_t)n;
     pc.hist_scratch = nullptr;
-    if (pc.col_perm && tp.kernel == same_batch::TimePar::kPipeRelaxed && same::sym_kernel_supported(tp.Pv)) {
+    if (pc.col_perm && tp.family == same::Family::kSym) {
         HIP_TRY(tp.d_hist.ensure((size_t)columns * same::kSquelchHist));
         pc.hist_scratch = tp.d_hist;
     }
     sl.have_k = sl.timed;
     if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_k0, stream));
-    hipError_t e = wave ? same::launch_demod_relaxed(tp.Pv, tp.Sv, O, rx->d_taps, d_x, (uint32_t)(n / fb), rx->counter, stream, pc)
-                        : (tp.kernel == same_batch::TimePar::kPipeRelaxed ? launch_fm(tp.Pv, tp.Sv, O, rx->d_taps, d_x, (uint32_t)(n / fb), rx->counter, stream, pc)
-                                                                          : same::launch_demod_pipe(tp.Pv, tp.Sv, O, rx->d_taps, d_x, (uint32_t)(n / fb), rx->counter, stream, pc, false));
+    const hipError_t e = launch_family(tp.family, tp.Pv, tp.Sv, O, rx->d_taps, d_x, (uint32_t)(n / fb), rx->counter, stream, pc);
+    rx->last_family = tp.family;
     if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
     if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_k1, stream));
     // The channels' state afterwards: that of the chunk the hand-over chain ends in, as the host's stitch follows it --
@@ -2152,18 +2061,13 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
     TRY_OR_CLEAN(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return cleanup(fail(SAME_ENODEVICE, "device %d is %s; this build carries gfx950 code only", device, prop.gcnArchName));
-    rx->use_fast = same::fast_kernel_supported(rx->P);
-    rx->force_generic = (flags & SAME_BATCH_GENERIC_KERNEL) != 0;
-    // Relaxed arithmetic: asked for (SAME_BATCH_RELAXED), or implied by the time-parallel mode, whose contract is the
-    // same one (SAME_RELAXED=0 keeps that mode on the strict pipeline kernel; =1 turns it on for any batch)
-    rx->relaxed = (((flags & (SAME_BATCH_RELAXED | SAME_BATCH_TIME_PARALLEL)) != 0 && rx->knob_relaxed >= 0) || rx->knob_relaxed > 0) &&
-                  rx->use_fast && !rx->force_generic &&
-                  (same::relaxed_kernel_supported(rx->P) || (rx->P.n_channels % same::kWave == 0u && same::pipe_relaxed_supported(fm_params(rx->P))));
-    // (a call of a time-parallel batch that is too short to be cut stays strict unless relaxed arithmetic was asked for)
-    // (... nor a batch of more than 16 384 channels, which is never cut: plan_chunks)
-    rx->relaxed_plain = rx->relaxed && ((flags & SAME_BATCH_RELAXED) != 0 || rx->knob_relaxed > 0 ||
-                                        ((flags & SAME_BATCH_TIME_PARALLEL) != 0 && n_channels > 16384u && n_channels % same::kWave == 0u &&
-                                         same::sym_kernel_supported(fm_params(rx->P))));
+    rx->want.relaxed = (flags & SAME_BATCH_RELAXED) != 0;
+    rx->want.time_parallel = rx->tp.enabled;
+    rx->want.generic = (flags & SAME_BATCH_GENERIC_KERNEL) != 0;      // (tests compare both kernels)
+    rx->mode = same::select_mode(rx->P, rx->want);
+    rx->plain = same::select_plain(rx->P, rx->mode, rx->want);
+    rx->Pfm = same::fm_params(rx->P);
+    rx->last_family = same::strict_family(rx->P, rx->mode);
     if (same::demod_lds_bytes(rx->P) > 160 * 1024)
         return cleanup(fail(SAME_EINVAL, "configuration needs %zu bytes of LDS per wavefront (limit 160 KiB)", same::demod_lds_bytes(rx->P)));
     TRY_OR_CLEAN(hipStreamCreateWithFlags(&rx->own_stream, hipStreamNonBlocking));
@@ -2617,28 +2521,7 @@ int same_batch_time_parallel_per_channel(const same_batch *rx) { return rx && rx
 
 const char *same_batch_kernel_name(const same_batch *rx)
 {
-    if (!rx) return "";
-    if (rx->tp.last_chunks > 1u) {
-        switch (rx->tp.kernel) {
-        case same_batch::TimePar::kWaveRelaxed: return "demod_relaxed_kernel";
-        case same_batch::TimePar::kPipeRelaxed: return same::sym_kernel_supported(rx->tp.Pv) ? "demod_sym_kernel" : "demod_pipe_kernel<fastmath>";
-        default: return "demod_pipe_kernel";
-        }
-    }
-    if (rx->relaxed_plain && rx->last_plain_fm) return rx->last_fm_sym ? "demod_sym_kernel" : "demod_pipe_kernel<fastmath>";
-    if (rx->relaxed_plain && rx->last_plain_wave) return "demod_relaxed_kernel";
-    if (rx->use_fast && !rx->force_generic) 
-    {
-        const uint32_t st = same::pipe_kernel_stages(rx->P);
-        return st != 0u ? "demod_pipe_kernel" : "demod_fast_kernel";
-    }
-    switch (rx->P.block_len) {
-    case 16: return "demod_kernel<B=16>";
-    case 8: return "demod_kernel<B=8>";
-    case 4: return "demod_kernel<B=4>";
-    case 2: return "demod_kernel<B=2>";
-    default: return "demod_kernel<B=1>";
-    }
+    return rx ? same::family_name(rx->last_family, rx->P.block_len) : "";
 }
 
 // ------------------------------------------------------------------------------------

@@ -41,6 +41,8 @@ void builder_defaults(same_rx_builder &b, uint32_t input_rate);
 int derive_params(const same_rx_builder &b, uint32_t n_channels, Params &P,
                   std::vector<float> &taps);
 
+// longest block that can hold at most one TED instant for this configuration
+uint32_t max_block_len(const Params &P);
 // largest B in {16,8,4,2,1} such that a TED cannot fire twice within B samples
 uint32_t choose_block_len(const Params &P);
 

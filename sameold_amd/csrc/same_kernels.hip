@@ -533,9 +533,6 @@ hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O,
                                uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream)
 { return launch_demod_ragged_t<int16_t>(P, S, O, taps, x, n_rows, counts, row_sub, counter0, stream); }
 
-size_t demod_lds_bytes(const Params &P)
-{ return (size_t)(2 * P.dc_len + P.win_ring) * kWave * sizeof(float); }
-
 hipError_t launch_init_state(const Params &P, const State &S, int is_reset, hipStream_t stream, uint32_t first_col)
 {
     if (first_col >= P.n_channels) return hipSuccess;

@@ -323,29 +323,17 @@ static constexpr size_t fast_lds_bytes()
     return (TAPF + (size_t)((MIRROR ? 2 * RING - kB : RING) + (DENSE ? 0 : kSquelchHist) + ((DCL <= kB && DCL <= 16) ? 0 : 2 * DCL)) * kWave) * sizeof(float);
 }
 
-// The mirrored window costs 16 KB of LDS per wavefront: 3 wavefronts fit a CU's 160 KB instead
-// of 4, so it is used while the batch needs at most 3 wavefronts per CU (and only for the
-// 42-tap filters, whose ring is 64 slots).
-static bool fast_use_mirror(const Params &P, uint32_t max_block)
-{
-    if (max_block < (uint32_t)kBlockMirror) return false;     // 18-sample blocks need the timing bound
-    if (P.knob_mirror != 0) return P.knob_mirror > 0 && P.ntaps == 42u;
-    return P.ntaps == 42u && (P.n_channels + kWave - 1) / kWave <= 3u * 256u;
-}
-
 template <int NT, int DCL, typename SampleT>
 static hipError_t launch_fast_cfg(const Params &P, const State &S, const Output &O, const float4 *taps,
                                   const SampleT *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream)
 {
     const uint32_t grid = (P.n_channels + kWave - 1) / kWave;
     constexpr bool CAN_MIRROR = (NT == 42);
-    const bool mirror = CAN_MIRROR && fast_use_mirror(P, max_block_len(P));
-    // more wavefronts than one per SIMD (1 024): the dense build, two per SIMD (22.05 kHz; SAME_FAST_DENSE=0/1 overrides)
+    const bool mirror = CAN_MIRROR && fast_use_mirror(P);
     constexpr bool CAN_DENSE = (NT == 42);
-    const bool dense = CAN_DENSE && !mirror && (P.knob_fast_dense != 0 ? P.knob_fast_dense > 0 : grid > 1024u);
+    const bool dense = CAN_DENSE && fast_use_dense(P);
     const size_t lds = mirror ? fast_lds_bytes<NT, DCL, CAN_MIRROR>() : (dense ? fast_lds_bytes<NT, DCL, false, CAN_DENSE>() : fast_lds_bytes<NT, DCL, false>());
-    // v_med3_f32 == f32::clamp unless a bound is -0.0 (or NaN, which the builder rejects)
-    const bool med3 = !(P.agc_min == 0.0f && std::signbit(P.agc_min)) && !(P.agc_max == 0.0f && std::signbit(P.agc_max));
+    const bool med3 = agc_clamp_is_med3(P);
 #define SAME_FAST_M(NFF, NFB, M3, MI)                                                                       \
     hipLaunchKernelGGL((demod_fast_kernel<NT, DCL, NFF, NFB, M3, MI, SampleT>), dim3(grid), dim3(kWave), lds, \
                        stream, P, S, O, taps, x, n_blocks, counter0)
@@ -361,26 +349,6 @@ static hipError_t launch_fast_cfg(const Params &P, const State &S, const Output 
 #undef SAME_FAST
 #undef SAME_FAST_M
     return hipGetLastError();
-}
-
-bool fast_kernel_supported(const Params &P)
-{
-    if (P.block_len != (uint32_t)kBlock || P.win_ring > 128u) return false;
-    const bool eq_ok = (P.eq_nff == 6u && P.eq_nfb == 4u) || (P.eq_nff == 1u && P.eq_nfb == 1u);
-    if (!eq_ok) return false;
-    if (P.ntaps >= 84u && max_block_len(P) < (uint32_t)kBlock48k) return false;   // their block is 32 samples
-    return (P.ntaps == 42u && P.dc_len == 16u) || (P.ntaps == 92u && P.dc_len == 35u) ||
-           (P.ntaps == 84u && P.dc_len == 32u);
-}
-
-uint32_t fast_win_ring(const Params &P) { return (P.ntaps + kBlock - 1 <= 64u) ? 64u : 128u; }
-
-// samples per block of the variant launch_demod_fast will pick for this batch
-uint32_t fast_block_len(const Params &P)
-{
-    if (pipe_kernel_selected(P)) return pipe_block_len(P);
-    if (P.ntaps == 42u && fast_use_mirror(P, max_block_len(P))) return (uint32_t)kBlockMirror;
-    return P.ntaps >= 84u ? (uint32_t)kBlock48k : (uint32_t)kBlock;
 }
 
 template <typename SampleT>

@@ -41,10 +41,7 @@ namespace same {
 // Geometry per sample rate (filter length NT): DC-blocker window, samples per block, window ring.
 // The ring is five blocks at every rate: NT - 1 samples back from an instant early in block s-1
 // reach into block s-4 (41 = 2*20 + 1, 91 = 2*32 + 27, 83 = 2*32 + 19) while stage 1 writes block s.
-// Samples per block at 48 / 44.1 kHz (bounds 43 / 39, one instant per block).  Measured at 16 384
-// channels x 2 s: 48 kHz 6.03 ms with 32, 6.75 with 36, 6.48 with 40 (stage 1's registers);
-// 44.1 kHz 5.35 ms with 32, 5.20 with 36.
-constexpr int kBlockPipe48 = 32, kBlockPipe44 = 36;
+// (samples per block: kBlockPipe22 / kBlockPipe48 / kBlockPipe44, same_select.h)
 template <int NT> struct PipeGeom;
 template <> struct PipeGeom<42> { static constexpr int DCL = 16, B = kBlockPipe22; };   // 22.05 kHz
 template <> struct PipeGeom<92> { static constexpr int DCL = 35, B = kBlockPipe48; };       // 48 kHz
@@ -1302,44 +1299,6 @@ static constexpr size_t pipe_lds_bytes()
             (size_t)(kSquelchHist + 2 * LY::RING - LY::B) * kWave) * sizeof(float);
 }
 
-// The pipeline pays while SIMDs are idle.  Whole groups of 64 channels only.  Measured at
-// 22.05 kHz: it wins up to 32 768 channels (two workgroups of four wavefronts per CU), the
-// one-wavefront kernel from 49 152 on.  At 44.1 / 48 kHz a workgroup's window ring is 72 KB of
-// the CU's 160 KB of LDS, so one workgroup per CU and 16 384 channels at a time; two rounds of
-// them (32 768 channels: 13.1 ms for 2 s at 48 kHz) still beat one wavefront per 64 channels
-// (16.0 ms), three do not.  Returns 0 (not selected) or non-zero.
-// v_med3_f32 == f32::clamp unless a bound is -0.0 (or NaN, which the builder rejects)
-static bool agc_clamp_is_med3(const Params &P)
-{ return !(P.agc_min == 0.0f && std::signbit(P.agc_min)) && !(P.agc_max == 0.0f && std::signbit(P.agc_max)); }
-
-// channels per workgroup: 16 while that still leaves the batch within one workgroup per CU
-// (default equalizer only: fewer kernels to build), else 64
-static uint32_t pipe_lanes(const Params &P)
-{
-    if (!(P.eq_nff == 6u && P.eq_nfb == 4u) || !agc_clamp_is_med3(P)) return kWave;
-    if (P.knob_pipe_lanes == 16 || P.knob_pipe_lanes == 32 || P.knob_pipe_lanes == 64) return (uint32_t)P.knob_pipe_lanes;
-    if (P.n_channels <= 16u * 256u && P.n_channels % 16u == 0u) return 16u;
-    if (P.n_channels <= 32u * 256u && P.n_channels % 32u == 0u) return 32u;
-    return kWave;
-}
-
-uint32_t pipe_kernel_stages(const Params &P)
-{
-    const bool r22 = P.ntaps == 42u && P.dc_len == 16u, r48 = P.ntaps == 92u && P.dc_len == 35u,
-               r44 = P.ntaps == 84u && P.dc_len == 32u;
-    if (!(r22 || r48 || r44) || (P.n_channels % pipe_lanes(P)) != 0u) return 0;
-    if (!((P.eq_nff == 6u && P.eq_nfb == 4u) || (P.eq_nff == 1u && P.eq_nfb == 1u))) return 0;
-    if (P.block_len != 16u || max_block_len(P) < (r22 ? (uint32_t)kBlockMirror : pipe_block_len(P))) return 0;
-    if (P.knob_pipe != 0) return P.knob_pipe > 0 ? 4u : 0u;
-    // beyond two workgroups per CU the pipeline runs in rounds; 22.05 kHz, sustained 2 s launches with the transport layer on
-    // (tools/big_sustained_strict.py): 65 536 channels 7.97 ms against the one-wavefront kernel's 9.06, 131 072: 15.6 against
-    // 15.0, 262 144: 30.5 against 29.2
-    return P.n_channels <= (r22 ? 65536u : 32768u) ? 4u : 0u;
-}
-bool pipe_kernel_selected(const Params &P) { return pipe_kernel_stages(P) != 0u; }
-uint32_t pipe_block_len(const Params &P)
-{ return P.ntaps == 42u ? (uint32_t)kBlockPipe22 : (P.ntaps == 92u ? (uint32_t)PipeGeom<92>::B : (uint32_t)PipeGeom<84>::B); }
-
 template <int NT, int NFF, int NFB, bool M3, bool SHARE, int LANES, bool SPLIT, typename SampleT, bool FM = false>
 static hipError_t launch_pipe_one(const Params &P, const State &S, const Output &O, const float4 *taps,
                                   const SampleT *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
@@ -1393,25 +1352,18 @@ static hipError_t launch_pipe_cfg(const Params &P, const State &S, const Output 
             return launch_pipe_one<NT, 1, 1, true, false, 64, true, SampleT, true>(P, S, O, taps, x, n_blocks, counter0, stream, K);
         }
     }
-    // two workgroups per CU (22.05 kHz only, where their LDS allows it): the register-capped build, with
-    // stage 2 split (same box, 32 768 channels x 2 s: 4.27-4.29 ms unsplit, 4.18-4.24 ms split).  Which stages
-    // of the two workgroups meet on a SIMD makes no measurable difference there (dealt by SIMD id: like + like
-    // 4.14 ms, stage 1 + 2 and 3 + 4 4.19 ms, 1 + 4 and 2 + 3 4.20 ms, by wavefront number 4.20 ms, one box),
-    // so they are left where they fall.
+    // the form of a strict launch: two workgroups per CU or one, stage 2 split or not (pipe_share, pipe_split)
     constexpr bool CAN_SHARE = (NT == 42);
-    const bool share = CAN_SHARE && (P.knob_pipe_share != 0 ? P.knob_pipe_share > 0 : P.n_channels > 16384u);
+    const bool share = CAN_SHARE && pipe_share(P);
     const bool med3 = agc_clamp_is_med3(P);
-    const bool share_split = P.knob_pipe_split != 0 ? P.knob_pipe_split > 0 : true;
+    const bool split = pipe_split(P, share);
 #define SAME_PIPE_LAUNCH(NFF, NFB, M3)                                                                                  \
-    (share ? (share_split ? launch_pipe_one<NT, NFF, NFB, M3, CAN_SHARE, 64, CAN_SHARE, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K)    \
+    (share ? (split ? launch_pipe_one<NT, NFF, NFB, M3, CAN_SHARE, 64, CAN_SHARE, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K)    \
                           : launch_pipe_one<NT, NFF, NFB, M3, CAN_SHARE, 64, false, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K))     \
            : launch_pipe_one<NT, NFF, NFB, M3, false, 64, false, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K))
-    const uint32_t lanes = pipe_lanes(P);
+    const uint32_t lanes = pipe_workgroup_channels(P);
     if (P.eq_nff == 6u && P.eq_nfb == 4u && med3 && !share) {
-        // the default configuration: narrow workgroups for small batches, and stage 2 split with stage 4's
-        // wavefront wherever stage 2 is (one of) the longest -- everywhere except 64-channel workgroups at
-        // 22.05 kHz, whose symbol stage is longer still
-        const bool split = P.knob_pipe_split != 0 ? P.knob_pipe_split > 0 : (NT != 42 || lanes != kWave);
+        // the default configuration: narrow workgroups for small batches, stage 2 split or not
 #define SAME_PIPE_LANES_LAUNCH(LN)                                                                                          \
         (split ? launch_pipe_one<NT, 6, 4, true, false, LN, true, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K)    \
                : launch_pipe_one<NT, 6, 4, true, false, LN, false, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K))
@@ -1441,15 +1393,6 @@ hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, c
 hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K, bool relaxed)
 { return launch_pipe_t<int16_t>(P, S, O, taps, x, n_blocks, counter0, stream, K, relaxed); }
-// The FASTMATH build exists for the three rates the pipeline is built for, in 64-channel workgroups (whole groups of 64
-// state columns), default or disabled equalizer, a non-negative AGC floor
-bool pipe_relaxed_supported(const Params &P)
-{
-    const bool geom = (P.ntaps == 42u && P.dc_len == 16u) || (P.ntaps == 92u && P.dc_len == 35u) || (P.ntaps == 84u && P.dc_len == 32u);
-    return geom && (P.n_channels % kWave) == 0u && P.agc_min >= 0.0f && pipe_kernel_stages(P) != 0u &&
-           pipe_lanes(P) == kWave && ((P.eq_nff == 6u && P.eq_nfb == 4u) || (P.eq_nff == 1u && P.eq_nfb == 1u));
-}
-uint32_t pipe_workgroup_channels(const Params &P) { return pipe_lanes(P); }
 
 }  // namespace same
 

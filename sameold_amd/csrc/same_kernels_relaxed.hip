@@ -767,32 +767,7 @@ __global__ __launch_bounds__(2 * kWave, 2) void demod_duo_kernel(Params P, State
 // ---------------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------------
-// The relaxed kernel exists for 22.05 kHz with the reference's default DC-blocker length, the default or the disabled
-// equalizer, a non-negative AGC floor (|x * gain| = |x| * gain) and a timing loop that cannot put three instants
-// into one sub-block.
-bool relaxed_kernel_supported(const Params &P)
-{
-    if (!(P.ntaps == 42u && P.dc_len == 16u && P.win_ring >= 64u)) return false;
-    if (!((P.eq_nff == 6u && P.eq_nfb == 4u) || (P.eq_nff == 1u && P.eq_nfb == 1u))) return false;
-    if (!(P.agc_min >= 0.0f)) return false;
-    return max_block_len(P) >= (uint32_t)kBlockMirror;
-}
-// (Since round 4 these kernels take relaxed batches that are not whole groups of 64 channels, time-parallel calls beyond
-// 16 384 channels and what SAME_RELAXED_KERNEL sends them; everything else runs the symbol-paced pipeline, which is faster
-// at every channel count under sustained launches: same_batch.cpp.)
-// Which form runs a launch over P.n_channels state columns: 1 duo (two wavefronts per 64 columns) while that leaves the
-// launch at no more than two wavefronts per SIMD (65 536 columns), 0 solo beyond -- or what SAME_RELAXED_KERNEL asks for.  Whole groups
-// of 64 columns for duo.  (A third form -- sample phase | filters + timing loop | symbol path on three wavefronts, 18-sample
-// sub-blocks, the symbol stage on every step or on every other -- was built and measured in round 3: 3.9-4.1 ms where the
-// pipeline's FASTMATH build takes 3.8; not kept.)
-uint32_t relaxed_kernel_kind(const Params &P)
-{
-    const bool whole = (P.n_channels % kWave) == 0u;
-    if (P.knob_relaxed_kernel == 1 || !whole) return 0u;
-    if (P.knob_relaxed_kernel == 2) return 1u;
-    return P.n_channels <= 65536u ? 1u : 0u;      // (measured, 2 s launches: 65 536 columns duo 6.5 against solo 7.0 ms; 81 920: 11.8 against 9.0; 98 304: 12.1 against 9.8)
-}
-uint32_t relaxed_block_len(const Params &P) { (void)P; return (uint32_t)RelaxLayout<42>::B; }
+static_assert(RelaxLayout<42>::B == kBlockRelaxed, "same_select.h decides with this block");
 
 template <int NFF, int NFB, typename SampleT, bool CM, bool TICKS, int OCC>
 static void launch_relaxed_one(const Params &P, const State &S, const Output &O, const float4 *taps, const SampleT *x,
@@ -819,7 +794,6 @@ static hipError_t launch_relaxed_t(const Params &P, const State &S, const Output
     const bool cm = K.n_chunks > 1u && K.col_row0 != nullptr;
     if (cm && !std::is_same<SampleT, float>::value) return hipErrorInvalidValue;
     if (P.n_channels > 0x7fffffffu / 64u / sizeof(SampleT)) return hipErrorInvalidValue;   // a block of rows within a buffer resource
-    const uint32_t grid = (P.n_channels + kWave - 1) / kWave;
     const bool eq64 = P.eq_nff == 6u && P.eq_nfb == 4u, ticks = P.ticks != 0u;
     const uint32_t kind = relaxed_kernel_kind(P);
     if (kind == 1u) {
@@ -832,8 +806,7 @@ static hipError_t launch_relaxed_t(const Params &P, const State &S, const Output
 #undef SAME_DUO_GO
         return hipGetLastError();
     }
-    // more wavefronts than SIMDs: the build for two per SIMD; otherwise a wavefront has its SIMD's registers to itself
-    const bool wide = grid <= 1024u && !ticks && std::is_same<SampleT, float>::value;
+    const bool wide = relaxed_solo_wide(P) && std::is_same<SampleT, float>::value;
 #define SAME_RELAX_GO(NFF, NFB, CM_, TK, OC) launch_relaxed_one<NFF, NFB, SampleT, CM_, TK, OC>(P, S, O, taps, x, n_blocks, counter0, stream, K)
     if constexpr (std::is_same<SampleT, float>::value) {
         if (cm) {

@@ -2029,16 +2029,7 @@ __global__ __launch_bounds__(SymGeom<NT>::HALVES * kSymRoles * kWave, NT == 42 ?
 // ---------------------------------------------------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------------------------------------------------
-// 22.05 / 44.1 / 48 kHz with the reference's default DC-blocker length, the default or the disabled equalizer, a non-negative AGC
-// floor, whole groups of 64 state columns, and a timing loop whose shortest symbol is longer than a step (two instants at
-// least max_block_len + 1 samples apart each: 19 / 40 / 44) and whose filters stay inside the four finished blocks of the ring
-static uint32_t sym_rate_nt(const Params &P)
-{
-    if (P.ntaps == 42u && P.dc_len == 16u) return 42u;
-    if (P.ntaps == 92u && P.dc_len == 35u) return 92u;
-    if (P.ntaps == 84u && P.dc_len == 32u) return 84u;
-    return 0u;
-}
+// (which configurations the kernel takes: sym_kernel_supported, same_select.cpp)
 // Two translation units (round 6).  The 44.1 / 48 kHz instantiations are compiled a second time from this file by
 // same_kernels_sym_hi.hip (SYM_TU_HI), which the build schedules for instruction-level parallelism (`-mllvm
 // -amdgpu-sched-strategy=max-ilp`, sameold_amd/build.py): there six wavefronts share four SIMDs and a role's own dependent chains
@@ -2049,27 +2040,8 @@ static uint32_t sym_rate_nt(const Params &P)
 #if !defined(SAME_PROFILE) && !defined(SAME_SYM_TL)
 #define SYM_SPLIT_TU 1
 #endif
-#if !defined(SYM_TU_HI)
-uint32_t sym_block_len(const Params &P) { return sym_rate_nt(P) == 42u ? (uint32_t)SymLayout<42>::B : (uint32_t)SymLayout<92>::B; }
-bool sym_kernel_supported(const Params &P)
-{
-    static_assert(SymLayout<92>::B == SymLayout<84>::B && SymLayout<92>::NBLK == SymLayout<42>::NBLK, "one step length beyond 22.05 kHz");
-    if (P.knob_sym < 0) return false;
-    const uint32_t nt = sym_rate_nt(P);
-    if (nt == 0u || P.win_ring < 64u || P.win_ring < nt || (P.n_channels % kWave) != 0u) return false;
-    if (P.n_channels >= (1u << 22)) return false;                    // (the squelch history's 24-bit row pitch, SymSquelch::hptr)
-    if (!((P.eq_nff == 6u && P.eq_nfb == 4u) || (P.eq_nff == 1u && P.eq_nfb == 1u))) return false;
-    if (!(P.agc_min >= 0.0f)) return false;
-    const uint32_t B = sym_block_len(P), apart = max_block_len(P) + 1u;
-    if (!(2u * apart > B)) return false;                             // at most one symbol per lane and step
-    // How far back a filter reaches from the end of the finished samples: a lane completes its symbol up to B behind it, one more
-    // B - apart after a symsync.reset() (the next instant completes a symbol by itself), the symbol's first instant lies up to
-    // period_max + alpha + 0.5 (+ rounding) before its second, and the filter takes ntaps - 1 samples before that.
-    const float a = P.alpha_unlocked > P.alpha_locked ? P.alpha_unlocked : P.alpha_locked;
-    const uint32_t reach = (2u * B - apart) + 1u + (uint32_t)std::ceil(P.period_max + a + 1.5f) + (nt - 1u);
-    return reach <= (uint32_t)(SymLayout<42>::NBLK - 2) * B;
-}
-#endif      // !SYM_TU_HI
+static_assert(SymLayout<42>::B == kSymStep22 && SymLayout<92>::B == kSymStepHi && SymLayout<84>::B == kSymStepHi && SymLayout<42>::NBLK == kSymRingSteps &&
+              SymLayout<92>::NBLK == kSymRingSteps, "same_select.h decides with these steps and this ring");
 
 template <int NT, int NFF, int NFB, typename SampleT>
 static hipError_t launch_sym_one(const Params &P, const State &S, const Output &O, const float4 *taps, const SampleT *x,
@@ -2113,7 +2085,7 @@ static hipError_t launch_sym_hi_t(const Params &P, const State &S, const Output 
                                   uint32_t n_blocks, uint64_t counter0, hipStream_t stream, const PipeChunks &K)
 {
     const bool eq = P.eq_nff == 6u && P.eq_nfb == 4u;
-    if (sym_rate_nt(P) == 92u)
+    if (standard_rate_taps(P) == 92u)
         return eq ? launch_sym_one<92, 6, 4, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K) : launch_sym_one<92, 1, 1, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K);
     return eq ? launch_sym_one<84, 6, 4, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K) : launch_sym_one<84, 1, 1, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K);
 }
@@ -2144,7 +2116,7 @@ static hipError_t launch_sym_t(const Params &P, const State &S, const Output &O,
 {
     if (!sym_kernel_supported(P)) return hipErrorInvalidValue;
     const bool eq = P.eq_nff == 6u && P.eq_nfb == 4u;
-    if (sym_rate_nt(P) == 42u)
+    if (standard_rate_taps(P) == 42u)
         return eq ? launch_sym_one<42, 6, 4, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K) : launch_sym_one<42, 1, 1, SampleT>(P, S, O, taps, x, n_blocks, counter0, stream, K);
     return launch_demod_sym_hi(P, S, O, taps, x, n_blocks, counter0, stream, K);
 }

@@ -5,6 +5,7 @@
 
 #include "same_capture_dev.h"
 #include "same_device.h"
+#include "same_select.h"      // which of these launchers takes a launch, and the predicates callers use
 
 namespace same {
 
@@ -12,7 +13,6 @@ hipError_t launch_demod(const Params &P, const State &S, const Output &O, const 
                         const float *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
 hipError_t launch_demod(const Params &P, const State &S, const Output &O, const float4 *taps,
                         const int16_t *x, uint32_t n_samples, uint64_t counter0, hipStream_t stream);
-size_t demod_lds_bytes(const Params &P);
 // the ragged remainder of a ragged call (same_batch_process_*_ragged): rows [0, n_rows) of x, lane c consuming its first
 // min(counts[c] - row_sub, n_rows) of them (counts: device-readable, n_channels entries); leaves the state canonical at
 // counter0 + n_rows
@@ -20,16 +20,7 @@ hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O,
                                uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
 hipError_t launch_demod_ragged(const Params &P, const State &S, const Output &O, const float4 *taps, const int16_t *x,
                                uint32_t n_rows, const uint32_t *counts, uint32_t row_sub, uint64_t counter0, hipStream_t stream);
-// latency-optimised kernel for the standard rates (same_kernels_fast.hip); whole blocks of
-// fast_block_len() samples, the generic kernel takes the rest of a call
-// longest block that can hold at most one TED instant for this configuration (same_config.cpp)
-uint32_t max_block_len(const Params &P);
-bool fast_kernel_supported(const Params &P);
-uint32_t fast_block_len(const Params &P);   // samples per block of the fast kernel variant for this batch
 // four-stage wavefront pipeline (same_kernels_pipe.hip): up to 32 768 channels at 22.05 kHz
-bool pipe_kernel_selected(const Params &P);
-uint32_t pipe_kernel_stages(const Params &P);     // 0 (not selected) or non-zero
-uint32_t pipe_block_len(const Params &P);         // samples per block of the pipeline at this rate
 // relaxed: the FASTMATH build (relaxed arithmetic, same_relaxed_common.h); only where pipe_relaxed_supported(P)
 hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
@@ -37,29 +28,24 @@ hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, c
 hipError_t launch_demod_pipe(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                              const PipeChunks &chunks = PipeChunks{}, bool relaxed = false);
-bool pipe_relaxed_supported(const Params &P);
 // symbol-paced pipeline (same_kernels_sym.hip): relaxed arithmetic, 22.05 kHz, 36-sample steps, whole groups of 64 state
 // columns; takes time-parallel chunks like the pipeline
-bool sym_kernel_supported(const Params &P);
-uint32_t sym_block_len(const Params &P);
 hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps,
                             const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                             const PipeChunks &chunks = PipeChunks{});
 hipError_t launch_demod_sym(const Params &P, const State &S, const Output &O, const float4 *taps,
                             const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                             const PipeChunks &chunks = PipeChunks{});
-uint32_t pipe_workgroup_channels(const Params &P);   // channels per workgroup the pipeline would use for this batch
 // relaxed-arithmetic throughput kernel (same_kernels_relaxed.hip): 22.05 kHz, one wavefront per 64 state columns,
 // whole blocks of relaxed_block_len() samples; takes time-parallel chunks like the pipeline
-bool relaxed_kernel_supported(const Params &P);
-uint32_t relaxed_block_len(const Params &P);      // samples per block of the form relaxed_kernel_kind(P) picks for P.n_channels columns
-uint32_t relaxed_kernel_kind(const Params &P);    // 0 solo (one wavefront per 64 columns), 1 duo (two) (same_kernels_relaxed.hip)
 hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
                                 const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                                 const PipeChunks &chunks = PipeChunks{});
 hipError_t launch_demod_relaxed(const Params &P, const State &S, const Output &O, const float4 *taps,
                                 const int16_t *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                                 const PipeChunks &chunks = PipeChunks{});
+// latency-optimised kernel for the standard rates (same_kernels_fast.hip); whole blocks of
+// fast_block_len() samples, the generic kernel takes the rest of a call
 hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,
                              const float *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream);
 hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, const float4 *taps,

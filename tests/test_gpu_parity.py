@@ -1022,3 +1022,34 @@ def test_pipelined_matched_filters_equal_the_chunk_loop_bit_for_bit(sa, n_chunks
         assert np.array_equal(o[..., 0:2], o[..., 2:4]), "demod_pair_relaxed_chunks differs from demod_pair_relaxed"
         assert np.array_equal(o[..., 0:2], o[..., 4:6]), "demod_pair_relaxed_42 differs from demod_pair_relaxed"
         assert float(out[..., 0].abs().max()) > 0.0
+
+
+# ------------------------------------------------------------------ the recorded kernel choice is what is launched
+def _recorded_kernel(rate, n_ch, flags):
+    """The ordinary launch's kernel in the row (rate, channels, flags, base) of tests/golden/kernel_choice.txt (the table
+    tests/test_kernel_choice_cpu.py holds sameold_amd/csrc/same_select.cpp to)."""
+    with open(os.path.join(GOLDEN, "kernel_choice.txt")) as f:
+        rows = [ln for ln in f if ln.startswith(f"{rate} {n_ch} {flags} base|")]
+    assert len(rows) == 1
+    short = rows[0].split("|")[2].split(":")[0]
+    return {"F": "demod_fast_kernel", "P": "demod_pipe_kernel", "PF": "demod_pipe_kernel<fastmath>", "S": "demod_sym_kernel",
+            "W": "demod_relaxed_kernel"}[short]
+
+
+def test_the_recorded_kernel_choice_is_what_is_launched(sa):
+    """One call of zeros per batch: same_batch_kernel_name() afterwards is the kernel the CPU-side table names for the
+    configuration -- 64, 100 and 4 112 channels at every standard rate, strict and relaxed, and two int16 batches beyond the
+    32 768- (48 kHz) and the 65 536-channel (22.05 kHz) limits of the strict pipeline."""
+    import torch
+    cases = [(rate, n_ch, relaxed, torch.float32, 2048) for rate in (22050, 44100, 48000) for n_ch in (64, 100, 4112)
+             for relaxed in (False, True)]
+    cases += [(48000, 32832, False, torch.int16, 1024), (22050, 65600, False, torch.int16, 1024)]
+    seen = set()
+    for rate, n_ch, relaxed, dtype, n in cases:
+        want = _recorded_kernel(rate, n_ch, "relaxed" if relaxed else "none")
+        rx = sa.SameReceiverBuilder(rate).build_batch(n_ch, relaxed=relaxed)
+        rx.process_tensor(torch.zeros((n, n_ch), dtype=dtype, device="cuda"))
+        rx.sync()
+        assert rx.kernel_name() == want, (rate, n_ch, relaxed)
+        seen.add(want)
+    assert seen == {"demod_pipe_kernel", "demod_fast_kernel", "demod_sym_kernel", "demod_relaxed_kernel"}
