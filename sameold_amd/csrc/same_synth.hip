@@ -113,6 +113,7 @@ __global__ __launch_bounds__(kWave) void synth_kernel(SynthParams sp, float *__r
         }
         if (sp.noise_sigma > 0.0f) {
             uint64_t r = splitmix64(ns);
+            // (16777217.0f is 2^24, the nearest f32: u1 = (k + 1) / 2^24 in (0, 1], the convention of the trial generator)
             float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777217.0f);
             float u2 = (float)(uint32_t)((r >> 8) & 0xffffffu) * (1.0f / 16777216.0f);
             float g = sqrtf(-2.0f * __logf(u1)) * cospif(2.0f * u2);
@@ -141,7 +142,8 @@ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
 // One burst per trial: 0.1 s + U(0, one symbol) of noise-only lead-in, 16 x 0xAB + the header
 // of "channel" t (same_synth_payload(seed, t)), then noise to the end of the buffer.  Trial t
 // runs at Eb/N0 = lo + (t mod n_grid) * step dB.  Eb = A^2/2 * Tb and N0 = 2 sigma^2 / fs for
-// real white noise sampled at fs, so sigma = A * sqrt(sps / (4 * EbN0)).
+// real white noise sampled at fs, so sigma = A * sqrt(sps / (4 * EbN0)), with Tb and sps = fs / 520.83 the nominal bit: the
+// trial's own clock skew moves its bit length, and with it its Eb, by up to 0.25 % (0.011 dB) and not its sigma.
 __global__ __launch_bounds__(kWave) void trials_kernel(TrialParams tp, float *__restrict__ x, size_t n_samples)
 {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
