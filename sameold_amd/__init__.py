@@ -1,7 +1,8 @@
 """sameold_amd -- MI355X-native batched SAME/EAS AFSK demodulator (hot path of sameold).
 
 The package holds only what the path needs: csrc/ (gfx950 HIP kernels + the C ABI of
-include/same_rx.h) and receiver.py (a Python mirror of SameReceiverBuilder/SameReceiver).
+include/same_rx.h) and receiver.py (a Python mirror of SameReceiverBuilder/SameReceiver); resample.py puts the device
+resampler of include/same_resample.h in front of a batch whose sources run at different rates.
 """
 from .receiver import (  # noqa: F401
     Event, SameBatchReceiver, SameError, SameReceiver, SameReceiverBuilder,
@@ -11,3 +12,4 @@ from .receiver import (  # noqa: F401
     decode_recordings, load_library, synth_afsk, synth_payload,
     AUDIO_END, AUDIO_END_FLUSH, AUDIO_END_MESSAGE, AUDIO_END_RESET, AUDIO_FIRST, AUDIO_TRUNCATED, AudioChunk, AudioJoiner,
 )
+from .resample import MixedRateReceiver, Resampler  # noqa: F401
