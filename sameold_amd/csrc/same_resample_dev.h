@@ -1,7 +1,8 @@
 // same_resample_dev.h -- the per-output arithmetic of the mixed-rate resampler (include/same_resample.h) as
-// __host__ __device__ code: no heap, no STL.  One lane per channel runs it on the device (same_resample.hip); the same text
-// compiles with a plain C++ compiler, where tests/helpers/resample_plan_main.cpp holds it bit for bit against the numpy
-// reference (tests/helpers/resample_reference.py) under ASan + UBSan.
+// __host__ __device__ code: no heap, no STL.  One lane per channel runs it on the device (same_resample.hip), or, in a
+// per-source call, one lane per output row of one channel; the same text compiles with a plain C++ compiler, where
+// tests/helpers/resample_plan_main.cpp and resample_sources_main.cpp hold it bit for bit against the numpy reference
+// (tests/helpers/resample_reference.py) under ASan + UBSan.
 //
 // The contract.  A channel converts r_in to r_out with L = r_out / g, M = r_in / g, g = gcd, through T taps per
 // phase, stored [phase p][tap j].  Output n of the channel's stream reads the source from k = floor(n M / L) downwards with the
@@ -117,6 +118,64 @@ SAME_HD inline void update_history(float *hist, size_t hs, uint32_t T, const Sam
     }
     for (uint32_t i = 0; i + m < H; ++i) hist[(size_t)i * hs] = hist[(size_t)(i + m) * hs];
     for (uint32_t q = 0; q < m; ++q) hist[(size_t)(H - m + q) * hs] = (float)x[(size_t)q * xs];
+}
+
+// ---- Per-source calls: a channel's samples are its own unit-stride buffer, and the lanes of a wavefront are
+// consecutive output rows of ONE channel.  Ratio, T and the tap table are then the same in every lane, and lanes differ in
+// phase; the taps are read from a second copy of the table stored [tap j][phase p] (taps_t[j * L + p] == taps[p * T + j]), in
+// which the phases of one tap step are neighbours.
+
+// phase_of(n + i) from ph0 = phase_of(n), for 0 <= i < 64, in 32-bit arithmetic: (n + i) M = k0 L + p0 + i M, and
+// p0 + i M < L + 63 M <= 1024 + 63 * 6144 < 2^19 (T <= kMaxT bounds M / L <= 6, so M <= 6 kMaxL).
+SAME_HD inline Phase lane_phase(const Phase &ph0, uint32_t i, uint32_t L, uint32_t M)
+{
+    const uint32_t q = ph0.p + i * M;
+    return Phase{ph0.k + q / L, q % L};
+}
+
+// eval for a unit-stride source and the [j][p] table: `taps_p` = taps_t + p, tap j at taps_p[j * L].  The same sums in the same
+// order; x[0 .. rel] are the only samples of the source it loads.
+template <typename SampleT>
+SAME_HD inline float eval_source(const float *taps_p, uint32_t L, uint32_t T, uint64_t rel, const SampleT *x, const float *hist, size_t hs)
+{
+    if (T == 1) return (float)x[rel];
+    if (rel + 1 >= (uint64_t)T) {
+        const SampleT *xk = x + rel;
+        float acc = 0.0f;
+        SAME_RS_UNROLL8
+        for (uint32_t j = 0; j < T; ++j) acc = acc + taps_p[(size_t)j * L] * (float)xk[-(ptrdiff_t)j];
+        return acc;
+    }
+    const uint32_t jx = (uint32_t)(rel + 1);                                   // taps 0 .. jx-1 read this call's buffer
+    float acc = 0.0f;
+    for (uint32_t j = 0; j < jx; ++j) acc = acc + taps_p[(size_t)j * L] * (float)x[rel - j];
+    for (uint32_t j = jx; j < T; ++j) acc = acc + taps_p[(size_t)j * L] * hist[(size_t)(T - 1 + (uint32_t)rel - j) * hs];
+    return acc;
+}
+
+// The outputs [row0, row1) of one channel's per-source call, row1 - row0 <= 64, as far as the call makes them: lane i takes
+// row row0 + i into y[i * ys].  A wavefront calls it with (lane, 64), a host loop with (0, 1); either way one 64-bit phase_of
+// per call, every row's phase from it.  `x`: the channel's in_count samples of this call; `taps_t`: the [j][p] tables.
+template <typename SampleT>
+SAME_HD inline void source_rows(const Desc &d, const Ratio &r, const float *taps_t, const SampleT *x, const float *hist, size_t hs,
+                                float *y, size_t ys, uint32_t row0, uint32_t row1, uint32_t lane, uint32_t lanes)
+{
+    if (row1 > d.out_count) row1 = d.out_count;
+    if (row0 >= row1) return;
+    const Phase ph0 = phase_of(d.n_out + row0, r.L, r.M);
+    const float *h = taps_t + r.tap_off;
+    for (uint32_t i = lane; i < row1 - row0; i += lanes) {
+        const Phase ph = lane_phase(ph0, i, r.L, r.M);
+        y[(size_t)i * ys] = eval_source(h + ph.p, r.L, r.T, ph.k - d.n_in, x, hist, hs);
+    }
+}
+
+// The history behind a per-source call: update_history on the channel's own buffer.  Nothing of x is loaded when m == 0.
+template <typename SampleT>
+SAME_HD inline void update_history_source(float *hist, size_t hs, uint32_t T, const SampleT *x, uint32_t m)
+{
+    if (m == 0 || T == 1) return;
+    update_history(hist, hs, T, x, 1, m);
 }
 
 }  // namespace rs

@@ -20,6 +20,7 @@ struct ResamplePlan {
     uint32_t out_rate = 0;
     std::vector<rs::Ratio> ratios;           // at most rs::kMaxRatios, only ever appended to
     std::vector<float> taps;                 // every ratio's table, [p][j] at its tap_off
+    std::vector<float> taps_t;               // the same tables stored [j][p] (taps_t[off + j L + p] == taps[off + p T + j]): per-source calls
     std::vector<uint32_t> chan_rate, chan_ratio;
     std::vector<uint64_t> n_in, n_out;       // per channel, since its start or last reset
     std::vector<uint8_t> clear;              // per channel: reset since the last call that ran; its history is to be zeroed
@@ -78,11 +79,14 @@ struct ResamplePlan {
         if (ratios.size() >= rs::kMaxRatios) return SAME_EINVAL;
         const rs::Ratio r{L, M, T, (uint32_t)taps.size()};
         taps.resize(taps.size() + (size_t)T * L);
-        float *h = taps.data() + r.tap_off;
+        taps_t.resize(taps.size());
+        float *h = taps.data() + r.tap_off, *ht = taps_t.data() + r.tap_off;
         if (T == 1) h[0] = 1.0f;
         else
             for (uint32_t p = 0; p < L; ++p)
                 for (uint32_t j = 0; j < T; ++j) h[(size_t)p * T + j] = (float)prototype(p + j * L, r_in, out_rate, L, T);
+        for (uint32_t p = 0; p < L; ++p)
+            for (uint32_t j = 0; j < T; ++j) ht[(size_t)j * L + p] = h[(size_t)p * T + j];
         index = (uint32_t)ratios.size();
         ratios.push_back(r);
         return SAME_OK;

@@ -4,6 +4,7 @@ every channel from its own source rate to one output rate, and `MixedRateReceive
 
     rx = MixedRateReceiver(SameReceiverBuilder(22050).samedec(), rates=[48000, 8000, 22050, ...])
     rx.process(x, in_counts)        # x: CUDA tensor [n_rows, C], float32 or int16; channel c owns its first in_counts[c] rows
+    rx.process_sources(sources)     # or: one 1-D CUDA tensor (or None) per channel, each of its own length
     rx.sync(); events = rx.poll_events()
 
 The batch's events count in samples at the batch's rate; `source_position` maps a counter back to the channel's source.
@@ -45,6 +46,8 @@ def _lib() -> C.CDLL:
     sig("same_resampler_out_counts", C.c_int, vp, P(u32), P(u32), P(u32))
     sig("same_resampler_process_device", C.c_int, vp, vp, C.c_size_t, P(u32), vp, C.c_size_t, P(u32), vp)
     sig("same_resampler_process_device_i16", C.c_int, vp, vp, C.c_size_t, P(u32), vp, C.c_size_t, P(u32), vp)
+    sig("same_resampler_process_device_sources", C.c_int, vp, vp, P(u32), vp, C.c_size_t, P(u32), vp)
+    sig("same_resampler_process_device_sources_i16", C.c_int, vp, vp, P(u32), vp, C.c_size_t, P(u32), vp)
     sig("same_resampler_reset_channels", C.c_int, vp, P(u32), C.c_size_t, P(u32))
     sig("same_resampler_channel_input_counter", u64, vp, u32)
     sig("same_resampler_channel_output_counter", u64, vp, u32)
@@ -150,6 +153,64 @@ class Resampler:
         out = self.process_device_ptr(x.data_ptr(), x.shape[0], in_counts, y.data_ptr(), y.shape[0], stream, x.dtype == torch.int16)
         return y, out
 
+    def process_source_ptrs(self, ptrs, in_counts, y_ptr: int, out_rows: int, stream: int = 0, i16: bool = False) -> np.ndarray:
+        """same_resampler_process_device_sources(_i16): `ptrs` is a uint64 numpy array of n_channels device addresses, channel
+        c's in_counts[c] contiguous samples at ptrs[c] (0 where the count is 0).  Returns out_counts.  The caller keeps every
+        source buffer and the output valid until the stream has passed the call."""
+        p = np.ascontiguousarray(ptrs, dtype=np.uint64)
+        if p.ndim != 1 or p.shape[0] != self.n_channels:
+            raise SameError(-1, f"ptrs: {p.shape} entries for {self.n_channels} channels; nothing was consumed")
+        k = _u32(in_counts, self.n_channels, "in_counts")
+        out = np.empty(self.n_channels, dtype=np.uint32)
+        fn = self._L.same_resampler_process_device_sources_i16 if i16 else self._L.same_resampler_process_device_sources
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), _p32(k), C.c_void_p(y_ptr), out_rows, _p32(out), C.c_void_p(stream)))
+        return out
+
+    def _process_ptrs(self, ptrs, in_counts, i16, device, y):
+        import torch
+        if y is None:
+            _, rows = self.out_counts(in_counts)
+            y = torch.empty((rows, self.n_channels), dtype=torch.float32, device=device)
+        assert y.is_cuda and y.is_contiguous() and y.dtype == torch.float32 and y.dim() == 2 and y.shape[1] == self.n_channels
+        stream = torch.cuda.current_stream(y.device).cuda_stream
+        return y, self.process_source_ptrs(ptrs, in_counts, y.data_ptr(), y.shape[0], stream, i16)
+
+    def process_sources(self, sources, y=None):
+        """sources: n_channels items, each a 1-D contiguous CUDA tensor -- the channel's next samples, all float32 or all int16
+        -- or None for a channel without samples in this call.  Resamples on torch's current stream into `y` (as `process`)
+        and returns (y, out_counts).  The caller keeps the tensors alive until the stream has passed the call."""
+        import torch
+        if len(sources) != self.n_channels:
+            raise SameError(-1, f"sources: {len(sources)} entries for {self.n_channels} channels; nothing was consumed")
+        ptrs = np.zeros(self.n_channels, np.uint64)
+        counts = np.zeros(self.n_channels, np.uint32)
+        dtype, device = None, None
+        for c, t in enumerate(sources):
+            if t is None:
+                continue
+            assert t.is_cuda and t.dim() == 1 and t.is_contiguous()
+            if t.dtype not in (torch.float32, torch.int16) or (dtype is not None and t.dtype != dtype):
+                raise TypeError("every source float32, or every source int16")
+            dtype, device = t.dtype, t.device
+            counts[c] = t.shape[0]
+            ptrs[c] = t.data_ptr() if t.shape[0] else 0
+        if device is None:
+            device = torch.device("cuda") if y is None else y.device
+        return self._process_ptrs(ptrs, counts, dtype == torch.int16, device, y)
+
+    def process_channel_major(self, x, in_counts, y=None):
+        """x: CUDA tensor [C, n_rows], float32 or int16, of which channel c owns the first in_counts[c] samples of its row: a
+        per-source call with the rows as the sources.  Returns (y, out_counts) like `process`."""
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 2 and x.shape[0] == self.n_channels
+        if x.dtype not in (torch.float32, torch.int16):
+            raise TypeError("float32 or int16 input")
+        k = _u32(in_counts, self.n_channels, "in_counts")
+        if k.size and k.max() > x.shape[1]:
+            raise SameError(-1, f"an in_count above n_rows = {x.shape[1]}; nothing was consumed")
+        ptrs = np.uint64(x.data_ptr()) + np.arange(self.n_channels, dtype=np.uint64) * np.uint64(x.shape[1] * x.element_size())
+        return self._process_ptrs(ptrs, k, x.dtype == torch.int16, x.device, y)
+
     def reset_channels(self, channels, rates=None) -> None:
         """The listed channels start again at this point of the stream (same_resampler_reset_channels); `rates`: their new
         source rates, one per channel listed, or None to keep them.  On an error nothing is reset."""
@@ -189,6 +250,18 @@ class MixedRateReceiver:
         no longer be running (two calls later, or `sync()`).  Returns the samples each channel's receiver was given."""
         y, out_counts = self.resampler.process(x, in_counts)
         self._sources.append(x)
+        if len(self._sources) > 2:
+            del self._sources[0]
+        if y.shape[0]:
+            self.batch.process_ragged(y, out_counts, LAYOUT_TIME_MAJOR)
+        return out_counts
+
+    def process_sources(self, sources) -> np.ndarray:
+        """sources: one 1-D contiguous CUDA tensor per channel (all float32 or all int16), or None: the channel's next samples
+        at rates[c], each of its own length.  As `process`: resampled on torch's current stream, handed to the batch's ragged
+        call, references to the sources and to the resampled tensor held for two calls or until `sync()`."""
+        y, out_counts = self.resampler.process_sources(sources)
+        self._sources.append(list(sources))
         if len(self._sources) > 2:
             del self._sources[0]
         if y.shape[0]:
