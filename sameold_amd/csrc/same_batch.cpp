@@ -1,6 +1,8 @@
 // same_batch.cpp -- host side of the C ABI: owns the per-channel receiver state in HBM,
-// launches the gfx950 kernels, and turns the device's append-only event log into the
+// launches the gfx950 kernels, and brings the device's append-only event log back for the
 // ordered event stream `SameReceiver::iter_events` yields (receiver.rs:119-130, 233-274).
+// What turns a launch's log into that stream once it is in host memory -- the replay, the event
+// and audio queues -- is host-only code in same_harvest.cpp; everything here launches, waits or copies.
 //
 // There is deliberately no CPU fallback here: if the HIP runtime or a gfx950 device is
 // missing, every compute entry point fails with SAME_ENODEVICE / SAME_EHIP.
@@ -8,44 +10,29 @@
 
 #include <algorithm>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <condition_variable>
 #include <cstring>
 #include <deque>
-#include <functional>
-#include <mutex>
 #include <new>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
 #include "../../include/same_rx.h"
 #include "same_config.h"
 #include "same_device.h"
+#include "same_harvest.h"
 #include "same_hipmem.h"
 #include "same_launch.h"
 #include "same_resets.h"
 #include "same_transport.h"
 
+using same::fail;        // (the one error channel: same_harvest.h)
+
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
+#define HIP_TRY(expr)                                                                     \
     do {                                                                                   \
         hipError_t _e = (expr);                                                            \
         if (_e != hipSuccess)                                                              \
@@ -54,157 +41,6 @@ int fail(int code, const char *fmt, ...)
     } while (0)
 
 }  // namespace
-
-// ------------------------------------------------------------------------------------
-// The host event queue.  A harvest of configs[1] brings ~110 000 link events per step; as 328-byte same_rx_event
-// records that was 36 MB written twice per step (thread-local parts, then the queue) -- 2 ms of host time under a
-// 2.7 ms launch.  The queue therefore holds 48-byte records, the burst / header bytes of the few events that carry any
-// sit in a byte arena beside them, and a same_rx_event is only made when a consumer asks for one
-// (same_batch_poll_events / _peek_events; same_batch_pack_bursts reads the records directly).
-struct QEvent {
-    uint32_t kind, channel;
-    uint64_t sample_counter, symbol_count;
-    uint32_t len, aux, aux2;
-    uint32_t n_bytes;                // payload bytes kept (min(len, SAME_EVENT_MAX_BYTES)), 0 = none
-    uint64_t payload;                // absolute offset of the payload in the arena
-};
-static_assert(sizeof(QEvent) == 48, "compact event record");
-template <typename T>
-struct PodQueue {                    // a plain growable array of PODs (no zero-fill on growth, appendable in slices)
-    T *buf = nullptr;
-    size_t n = 0, cap = 0;
-    size_t base = 0;                 // how many elements have left the front since the handle was made: buf[i] is number base + i
-    ~PodQueue() { std::free(buf); }
-    PodQueue() = default;
-    PodQueue(const PodQueue &) = delete;
-    PodQueue &operator=(const PodQueue &) = delete;
-    size_t size() const { return n; }
-    T *data() { return buf; }
-    const T *data() const { return buf; }
-    void clear() { base += n; n = 0; }
-    // drop the first `head` elements by moving the rest to the front; returns the new head (0)
-    size_t compact(size_t head)
-    {
-        if (head == 0) return 0;
-        if (head < n) std::memmove(buf, buf + head, (n - head) * sizeof(T));
-        n -= head;
-        base += head;
-        return 0;
-    }
-    // room for `extra` more elements; returns where they go, or nullptr when out of memory
-    T *grow(size_t extra)
-    {
-        if (n + extra > cap) {
-            const size_t want = (n + extra) + (n + extra) / 2 + 64;
-            void *p = std::realloc(buf, want * sizeof(T));
-            if (!p) return nullptr;
-            buf = static_cast<T *>(p);
-            cap = want;
-        }
-        T *at = buf + n;
-        n += extra;
-        return at;
-    }
-};
-using EventQueue = PodQueue<QEvent>;
-// a queued chunk of alert audio (same_batch_set_audio_capture): its samples are [at, at + n) of the sample arena (absolute index)
-struct AudioChunk {
-    uint32_t channel, flags;
-    uint64_t sample_counter, n;
-    uint64_t at;
-};
-using ByteArena = PodQueue<uint8_t>;     // payload bytes: element number = absolute offset
-// SAME_HOST_PROF (measurement builds: SAME_EXTRA_DEFS=SAME_HOST_PROF=1): time-stamp-counter totals of the replay's parts,
-// printed by same_debug_harvest_replay (one thread); nothing in the product build
-#ifdef SAME_HOST_PROF
-#include <x86intrin.h>
-static uint64_t g_hp[8];
-static const char *const g_hp_name[8] = {"range sort", "poll synthesis", "queue record + payload", "transport: burst", "transport: other", "after_event", "stitch scan", "-"};
-struct HpScope { int k; uint64_t t0; explicit HpScope(int k_) : k(k_), t0(__rdtsc()) {} ~HpScope() { g_hp[k] += __rdtsc() - t0; } };
-#define HP(k) HpScope hp_scope_##k(k)
-#else
-#define HP(k) do {} while (0)
-#endif
-struct HarvestPart {
-    std::vector<QEvent> out;             // payload = offset into `bytes` until the part is appended to the queue
-    std::vector<uint8_t> bytes;
-    std::vector<uint32_t> rearm;
-    std::vector<uint32_t> bursts;        // indices into out
-};
-// a queue record as the event the ABI hands out
-static void materialise(const QEvent &q, const uint8_t *arena, size_t arena_base, same_rx_event *ev)
-{
-    std::memset(ev, 0, sizeof(*ev));
-    ev->kind = q.kind; ev->channel = q.channel; ev->sample_counter = q.sample_counter; ev->symbol_count = q.symbol_count;
-    ev->len = q.len; ev->aux = q.aux; ev->aux2 = q.aux2;
-    if (q.n_bytes) std::memcpy(ev->bytes, arena + (q.payload - arena_base), q.n_bytes);
-}
-
-using same::TickSynth;
-
-// A few parked worker threads per batch for the harvest (replay, queue copy, burst packing): starting and joining 60
-// std::threads per launch costs more than the work some of them do, and eight ranks share one host.
-class WorkerPool {
-public:
-    ~WorkerPool()
-    {
-        { std::lock_guard<std::mutex> g(mu_); stop_ = true; }
-        cv_.notify_all();
-        for (std::thread &t : threads_) t.join();
-    }
-    // fn(0) .. fn(n - 1), the caller taking part; returns when all are done
-    void run(size_t n, const std::function<void(size_t)> &fn)
-    {
-        if (n <= 1) { if (n) fn(0); return; }
-        while (threads_.size() + 1 < n) threads_.emplace_back([this] { loop(); });
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            fn_ = &fn; next_ = 0; count_ = n; pending_ = n; ++generation_;
-        }
-        cv_.notify_all();
-        work();
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-private:
-    void work()
-    {
-        for (;;) {
-            size_t i;
-            const std::function<void(size_t)> *fn;
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                if (!fn_ || next_ >= count_) return;
-                i = next_++; fn = fn_;
-            }
-            (*fn)(i);
-            std::lock_guard<std::mutex> g(mu_);
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    void loop()
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || generation_ != seen; });
-                if (stop_) return;
-                seen = generation_;
-            }
-            work();
-        }
-    }
-    std::vector<std::thread> threads_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(size_t)> *fn_ = nullptr;
-    size_t next_ = 0, count_ = 0, pending_ = 0;
-    uint64_t generation_ = 0;
-    bool stop_ = false;
-};
 
 struct same_batch {
     same_rx_builder builder{};
@@ -300,8 +136,6 @@ struct same_batch {
         bool last_per_channel = false;
         same::Family family = same::Family::kPipe;            // which kernel runs the chunks of the call being planned (plan_chunks)
         int knob_prologue = 0;                                // SAME_TP_PROLOGUE=0: init kernel, fill and cursor reset as separate launches (A/B measurements)
-        std::vector<int64_t> sym_off;        // per channel: reported symbol count - the device's
-        std::vector<TickSynth> synth;
     } tp;
     uint64_t launch_seq = 0;
     hipStream_t copy_stream = nullptr;   // read-back of finished launches, beside the compute stream
@@ -337,7 +171,6 @@ struct same_batch {
     same::Family last_family = same::Family::kGeneric;
     bool sym_launched = false;       // an ordinary launch has run the symbol-paced pipeline (until then its name is the FASTMATH build's, whose place it takes)
     bool debug = false;              // SAME_DEBUG: harvest statistics on stderr
-    int host_threads = 0;            // SAME_HOST_THREADS: harvest threads (0 = choose)
     // staging for host / channel-major inputs
     same::DevBuf<void> d_stage, d_stage2;
     same::DevBuf<void> d_upload;                            // host-buffer entry points: grow-only upload slab
@@ -347,23 +180,6 @@ struct same_batch {
     bool timing = false;
     bool have_timing = false;
     float last_demod_ms = 0.0f;         // the demodulation kernel alone (= last_ms unless the launch brackets planning kernels too)
-    // ordered host-side event queue
-    EventQueue queue;                   // events not yet polled: [queue_head, size)
-    size_t queue_head = 0;
-    ByteArena arena;                    // their payload bytes
-    std::vector<same_rx_event> peeked;  // same_batch_peek_events: the queued events, materialised (328 bytes each) ...
-    bool peeked_valid = false;          // ... and whether it still mirrors queue[peeked_head ..) (a harvest appends: invalid)
-    bool peeked_release = false;        // the queue ran empty under same_batch_drop_events: the caller may still be reading the view; freed by the next call that ends its life
-    size_t peeked_head = 0;
-    std::vector<size_t> burst_seq;      // event numbers (EventQueue::base + index) of the queued SAME_LINK_BURST events, ascending
-    size_t burst_seq_head = 0;          // entries before this one have been polled or dropped
-    std::vector<HarvestPart> parts;     // per host thread, kept between harvests for their capacity
-    WorkerPool workers;
-    // transport layer, one assembler per channel (unless SAME_BATCH_LINK_ONLY)
-    // (two arrays: one cache line per channel that every poll touches, and the burst bytes / message texts: same_transport.h)
-    std::vector<same::TransportHot> thot;
-    std::vector<same::TransportCold> tcold;
-    same::TransportRef tr(uint32_t c) { return same::TransportRef(thot[c], tcold[c]); }
     same::PinnedBuf<uint64_t> h_wake; // host mirror of State::wake_sample (n_channels words, zero = unarmed)
     // A ragged launch moves the device's wake-up instants itself (the ragged kernel), in stream order.  From the first one on the
     // host's re-arming of the table is stream-ordered as well (behind the launch in flight, with its shifts added), so that an
@@ -379,20 +195,18 @@ struct same_batch {
     // per-channel resets (same_batch_reset_channels): where each half of a reset is due, the channels' counter bases
     same::ResetLedger resets;
     std::vector<uint32_t> reset_list, reset_now, reset_cols;       // scratch: the entry point's, the reset kernel's list
+    // the host half of the harvest (same_harvest.h): the ordered host-side event queue, and the channels' host state (transport
+    // layer, time-parallel symbol clocks) with the replay of a launch's log over it, its worker threads and SAME_HOST_THREADS
+    same::EventLog events;
+    same::Replay replay{resets, events};
     // alert audio per message (same_batch_set_audio_capture)
     struct Audio {
         size_t per_launch = 0;                   // pool samples per slot; 0: capture is off
         same::DevBuf<same::cap::Rec> d_rec;      // per channel: the device's capture record
-        std::vector<uint8_t> open;               // per channel: a capture is open as far as the queued chunks go (END_RESET chunks)
         uint64_t flush_at = UINT64_MAX;          // batch counter where the running same_batch_flush began
-        PodQueue<AudioChunk> queue;              // chunks not yet dropped: [head, size)
-        size_t head = 0;
-        PodQueue<float> samples;                 // their samples (element number = absolute index)
-        std::vector<same_audio_chunk> view;      // same_batch_peek_audio
+        same::AudioLog log;                      // the queued chunks, and which channels have a capture open
     } audio;
 };
-
-static void release_stale_view(same_batch *rx);
 
 namespace {
 
@@ -481,9 +295,9 @@ void read_knobs(same_batch *rx)
     rx->P.knob_fast_dense = tri("SAME_FAST_DENSE");
     rx->P.knob_sym = tri("SAME_SYM");
     rx->want.sym_max_channels = (uint32_t)std::max(0, num("SAME_SYM_MAX", 1 << 30));     // (measurement knob: up to where an ordinary relaxed launch takes the symbol-paced pipeline; default: always)
-    rx->debug = std::getenv("SAME_DEBUG") != nullptr;
+    rx->debug = rx->replay.debug = std::getenv("SAME_DEBUG") != nullptr;
     { const char *e = std::getenv("SAME_RECORD_HARVEST"); rx->record_path = e ? e : ""; }
-    rx->host_threads = std::max(0, num("SAME_HOST_THREADS", 0));
+    rx->replay.host_threads = std::max(0, num("SAME_HOST_THREADS", 0));
     rx->tp.sort_mode = num("SAME_TP_SORT", -1);
     rx->tp.knob_plan_stream = tri("SAME_TP_PLAN_STREAM");
     rx->tp.knob_prologue = tri("SAME_TP_PROLOGUE");
@@ -543,18 +357,11 @@ hipError_t launch_family(same::Family f, const same::Params &P, const same::Stat
     return hipErrorInvalidValue;
 }
 
-// The host half of a reset of channel c at stream position `pos` (same_batch_reset_channels): the transport layer goes Idle and
-// forgets its bursts, pending message and forced-EOM instant (receiver.rs:195-196); the time-parallel symbol clock restarts at
-// `pos` (the device's symbol counter of the channel restarts there too); the channel's wake-up entry is cleared (the reset kernel
-// clears the device's copy)
+// The host half of a reset of channel c at stream position `pos` (same_batch_reset_channels): the channel's host state
+// (Replay::reset_channel); the channel's wake-up entry is cleared (the reset kernel clears the device's copy)
 void reset_channel_host(same_batch *rx, uint32_t c, uint64_t pos)
 {
-    if (!rx->thot.empty()) rx->tr(c).reset();
-    if (rx->tp.enabled) {
-        rx->tp.sym_off[c] = 0;
-        rx->tp.synth[c].reset();
-        rx->tp.synth[c].a_t = pos;
-    }
+    rx->replay.reset_channel(c, pos);
     if (rx->h_wake) rx->h_wake[c] = 0;
 }
 
@@ -577,406 +384,22 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
     return SAME_OK;
 }
 
-// The host half of a harvest: the launch's ordered event log, burst pool, hand-over instants and chunk geometry are in the
-// slot's host buffers; order each column's records, replay the channels (stitch + transport layer) on the worker threads and
-// append to the queue.  Touches no device: same_debug_harvest_replay runs it on a recorded launch without one.
-// Before a harvest appends to the queue.  A consumer that always polls less than is pending never drains the queue: reclaim the
-// polled prefix once it is at least as large as what is still waiting (amortised O(1) per event).
-void prepare_queue_append(same_batch *rx)
-{
-    rx->peeked_valid = false;                 // (the queue is about to move and grow: a materialised view of it is stale)
-    release_stale_view(rx);
-    if (rx->queue_head && rx->queue_head >= rx->queue.size() - rx->queue_head) {
-        rx->queue_head = rx->queue.compact(rx->queue_head);
-        // ... and the payload bytes in front of the first record that is still queued
-        size_t keep_from = rx->arena.base + rx->arena.size();
-        for (size_t i = 0; i < rx->queue.size(); ++i)
-            if (rx->queue.data()[i].n_bytes) { keep_from = (size_t)rx->queue.data()[i].payload; break; }
-        rx->arena.compact(keep_from - rx->arena.base);
-    }
-}
-
-struct HarvestTimes { std::chrono::steady_clock::time_point sorted, replayed; uint32_t n_threads = 1; };
-// what it reads of a launch: the slot's landing buffers, or a recorded launch's (same_debug_harvest_replay)
-struct HarvestInput {
-    const uint32_t *first;           // [columns + 1] the columns' ranges of `events`
-    same::DevEvent *events;          // each range is sorted in place
-    const uint8_t *bursts;
-    const uint64_t *handover;        // a time-parallel launch's
-    const uint32_t *geom;            // ... with per-channel boundaries: own_start | row0
-};
-int harvest_host(same_batch *rx, same_batch::Slot &sl, const HarvestInput &in, uint32_t n_events, uint32_t n_bursts, std::vector<uint32_t> &rearm,
-                 HarvestTimes &times)
-{
-    const bool dbg = rx->debug;
-    const same::DevEvent *evs = in.events;
-    const uint8_t *bursts = in.bursts;
-    const uint32_t n_ch = rx->P.n_channels;
-    const uint32_t n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;     // state columns of the launch
-    // Per column the device emits in time order (a lane takes its log slots one after the other); across lanes the
-    // atomic cursor interleaves.  The device has counted the events per column and moved the records into column
-    // ranges (launch_event_sort: `evs` is that ordered copy, a record's `channel` holding its index in the log); inside
-    // a range they stand in the order the scatter's atomics landed, and the replay threads sort each range (a handful
-    // of records) back into log order = time order before they walk it.
-    // (slots a wavefront reserved but did not use carry kDevEventNone and were skipped there)
-    std::vector<uint32_t> first(in.first, in.first + n_bins + 1u);
-    same::DevEvent *evs_mut = in.events;
-    const uint32_t n_real = first[n_bins];
-    if (n_real > n_events) return fail(SAME_EHIP, "internal: event sort counted %u of %u events", n_real, n_events);
-    // (what follows indexes the ordered copy directly)
-    struct Identity { uint32_t operator[](uint32_t i) const { return i; } } order;
-    if (dbg && sl.chunked && sl.per_channel) {
-        // how the per-channel boundaries came out: chunk lengths (own range + warm-up) and run-ons, in samples
-        const same::ChunkGeom &g = sl.geom;
-        const uint32_t *own = in.geom, *rows = in.geom + n_bins;
-        double len_sum = 0, run_sum = 0; uint64_t len_max = 0, run_max = 0, n_len = 0, n_run = 0, n_inf = 0, n_late = 0;
-        uint32_t worst_c = 0;
-        for (uint32_t k = 0; k + 1u < g.n_chunks; ++k)
-            for (uint32_t c = 0; c < n_ch; ++c) {
-                const uint64_t end = own[(size_t)(k + 1u) * n_ch + c], len = end - rows[(size_t)k * n_ch + c];
-                len_sum += (double)len; if (len > len_max) { len_max = len; worst_c = c; } ++n_len;
-                const uint64_t h = in.handover[(size_t)k * n_ch + c];
-                if (h == same::kNoHandover) { ++n_inf; continue; }
-                const uint64_t run = h - g.counter0 > end ? h - g.counter0 - end : 0;
-                run_sum += (double)run; run_max = std::max(run_max, run); ++n_run; n_late += run > 2u * g.block_len;
-            }
-        std::fprintf(stderr, "[same] longest piece on channel %u, its cuts:", worst_c);
-        for (uint32_t k = 0; k < g.n_chunks; ++k) std::fprintf(stderr, " %u", own[(size_t)k * n_ch + worst_c]);
-        std::fprintf(stderr, "\n");
-        std::fprintf(stderr, "[same] per-channel chunks: length mean %.0f max %llu samples; run-on mean %.0f max %llu, %llu of %llu columns ran on "
-                             "more than two blocks, %llu never handed over\n", len_sum / std::max<uint64_t>(n_len, 1), (unsigned long long)len_max,
-                     run_sum / std::max<uint64_t>(n_run, 1), (unsigned long long)run_max, (unsigned long long)n_late, (unsigned long long)n_run,
-                     (unsigned long long)n_inf);
-    }
-    // events per real channel, cumulative (a chunked launch spreads a channel over n_chunks columns)
-    std::vector<uint32_t> chan_first;
-    if (sl.chunked) {
-        chan_first.assign(n_ch + 1u, 0u);
-        for (uint32_t k = 0; k < sl.geom.n_chunks; ++k)
-            for (uint32_t c = 0; c < n_ch; ++c) chan_first[c + 1u] += first[k * n_ch + c + 1u] - first[k * n_ch + c];
-        for (uint32_t c = 0; c < n_ch; ++c) chan_first[c + 1u] += chan_first[c];
-    }
-    const std::vector<uint32_t> &cfirst = sl.chunked ? chan_first : first;
-    const bool link_only = (rx->flags & SAME_BATCH_LINK_ONLY) != 0;
-    const bool tp = rx->tp.enabled;
-    times.sorted = std::chrono::steady_clock::now();
-
-    // Channels are independent (one Transport each), so contiguous channel ranges are replayed
-    // on separate host threads; each produces its slice of the output queue, in order.
-    using Part = HarvestPart;
-    const double sps = (double)rx->P.input_rate / 520.83;
-    const uint64_t interburst = same::max_interburst_symbols(), history = same::max_history_duration();
-    // one device event -> the link event of channel c (+ the transport event it causes).  `off`: what
-    // the time-parallel mode adds to the device's symbol count (0 otherwise).
-    // (transport events arrive as same_rx_event from the transport layer: kept as a record + payload)
-    // (the stitch and the transport layer work on the device's counters, from the batch's first sample; a queue record counts
-    // from its channel's last reset: same_batch_reset_channels)
-    const bool msgs_only = rx->messages_only;
-    auto push_transport = [&](Part &part, const same_rx_event &tev, uint32_t c) {
-        if (msgs_only && tev.kind != SAME_TRANSPORT_MSG_START && tev.kind != SAME_TRANSPORT_MSG_END) return;
-        QEvent q{};
-        q.kind = tev.kind; q.channel = c; q.sample_counter = rx->resets.rebase(c, tev.sample_counter); q.symbol_count = tev.symbol_count;
-        q.len = tev.len; q.aux = tev.aux; q.aux2 = tev.aux2;
-        q.n_bytes = std::min<uint32_t>(tev.len, SAME_EVENT_MAX_BYTES);
-        if (tev.kind != SAME_TRANSPORT_MSG_START) q.n_bytes = 0;       // (only a header carries bytes)
-        q.payload = part.bytes.size();
-        if (q.n_bytes) part.bytes.insert(part.bytes.end(), tev.bytes, tev.bytes + q.n_bytes);
-        part.out.push_back(q);
-    };
-    auto feed = [&](Part &part, same_rx_event &tev, const same::DevEvent &d, uint32_t c, int64_t off) {
-        const uint64_t sym = (uint64_t)((int64_t)d.symbol_count + off);
-        auto poll = [&](uint64_t psym, uint64_t pt) {
-            if (rx->tr(c).on_link_event(same::kDevTick, pt, psym, nullptr, 0, rx->P.input_rate, &tev)) push_transport(part, tev, c);
-        };
-        if (tp && !link_only) {
-            HP(1);
-            rx->tp.synth[c].run_until(sym, d.sample_counter, sps, rx->tr(c).force_eom_at(), poll);
-        }
-        QEvent q{};
-        const uint8_t *payload = nullptr;
-        {
-        HP(2);
-        q.kind = d.kind; q.channel = c; q.sample_counter = rx->resets.rebase(c, d.sample_counter); q.symbol_count = sym;
-        if (d.kind == SAME_LINK_BURST) {
-            q.len = d.burst_len;
-            if (d.burst_slot < n_bursts) {
-                q.n_bytes = std::min<uint32_t>(d.burst_len, SAME_EVENT_MAX_BYTES);
-                payload = bursts + (size_t)d.burst_slot * same::kBurstCap;
-                q.payload = part.bytes.size();
-                if (!msgs_only) part.bytes.insert(part.bytes.end(), payload, payload + q.n_bytes);
-            } else {
-                q.len = 0;     // pool overflow: the burst bytes were lost (SAME_EOVERFLOW is reported)
-            }
-            if (!msgs_only) part.bursts.push_back((uint32_t)part.out.size());
-        }
-        if (d.kind <= SAME_LINK_BURST && !msgs_only) part.out.push_back(q);
-        }
-        if (!link_only) {
-#ifdef SAME_HOST_PROF
-            HpScope hp_tr(d.kind == SAME_LINK_BURST ? 3 : 4);
-#endif
-            if (rx->tr(c).on_link_event(d.kind, d.sample_counter, sym, payload, q.n_bytes, rx->P.input_rate, &tev)) push_transport(part, tev, c);
-            if (!tp && rx->tr(c).force_eom_dirty()) part.rearm.push_back(c);
-        }
-        { HP(5); if (tp && d.kind <= SAME_LINK_BURST) rx->tp.synth[c].after_event(d.kind, sym, d.sample_counter, interburst, history); }
-    };
-    // Time-parallel launch: the events of channel c, stitched from its chunks.  Chunk `cur` is kept up to
-    // its hand-over instant h (the end of the first block at or after its nominal end in which the
-    // device saw it idle), then the chunk that owns h takes over -- from h if it is idle there too,
-    // otherwise from its own next NoCarrier on (it was still busy with the tail of a burst it joined in
-    // the middle, or with a duplicate of the burst the previous chunk has just delivered).
-    auto stitch = [&](Part &part, same_rx_event &ev, uint32_t c) {
-        const same::ChunkGeom &g = sl.geom;
-        const uint64_t *hand = in.handover;
-        // per-channel boundaries: own_start[k][c] and row0[k][c] as the device planned them
-        const uint32_t *own = sl.per_channel ? in.geom : nullptr, *rows = sl.per_channel ? in.geom + n_bins : nullptr;
-        auto owner_of = [&](uint64_t h) -> uint32_t {
-            if (!own) return g.owner_of(h);
-            uint32_t k = 0;
-            while (k + 1u < g.n_chunks && g.counter0 + own[(size_t)(k + 1u) * n_ch + c] <= h) ++k;
-            return k;
-        };
-        TickSynth &ts = rx->tp.synth[c];
-        int64_t off = rx->tp.sym_off[c];
-        uint32_t cur = 0;
-        uint64_t keep_after = 0;
-        for (;;) {
-            const uint32_t col = cur * n_ch + c;
-            const uint64_t h = hand[col];
-            const uint64_t upto = std::min(h, sl.end_blocks);
-            bool rebased = cur == 0;
-            for (uint32_t i = first[col]; i < first[col + 1u]; ++i) {
-                const same::DevEvent &d = evs[order[i]];
-                if (d.sample_counter <= keep_after) continue;
-                if (d.sample_counter > upto) break;
-                if (!rebased) {
-                    // continue the channel's symbol clock: the last reported event plus the nominal symbol rate
-                    const int64_t est = (int64_t)ts.a_sym + (int64_t)((double)(d.sample_counter - ts.a_t) / sps + 0.5);
-                    off = est - (int64_t)d.symbol_count;
-                    rebased = true;
-                }
-                feed(part, ev, d, c, off);
-            }
-            if (!rebased) {
-                // nothing reported from this chunk: its counter started at 0 at its first row
-                const uint64_t row0 = rows ? g.counter0 + rows[col] : g.counter0 + (uint64_t)cur * g.stride_blocks * g.block_len;
-                const int64_t est_end = (int64_t)ts.a_sym + (int64_t)((double)(sl.end_blocks - ts.a_t) / sps + 0.5);
-                off = est_end - (int64_t)((double)(sl.end_blocks - row0) / sps + 0.5);
-            }
-            if (h == same::kNoHandover) break;
-            const uint32_t nxt = owner_of(h);
-            if (nxt <= cur) break;
-            // the next chunk's link state at h, and where it is first idle from there on
-            const uint32_t ncol = nxt * n_ch + c;
-            uint32_t st = 0, j = first[ncol];
-            for (; j < first[ncol + 1u] && evs[order[j]].sample_counter <= h; ++j)
-                if (evs[order[j]].kind <= SAME_LINK_BURST) st = evs[order[j]].kind;
-            keep_after = h;
-            if (st == SAME_LINK_READING || st == SAME_LINK_BURST) {
-                // busy with a burst the previous chunk has already delivered (or with the garbage a chunk that
-                // joined in the middle of one makes of it): its events count from its next NoCarrier on
-                for (; j < first[ncol + 1u]; ++j)
-                    if (evs[order[j]].kind == SAME_LINK_NO_CARRIER) { keep_after = evs[order[j]].sample_counter; break; }
-            } else if (st == SAME_LINK_SEARCHING && ts.link == SAME_LINK_NO_CARRIER) {
-                // it has byte sync where the previous chunk has none yet (the two acquire a preamble some
-                // symbols apart): what follows -- Reading, Burst -- is real, so the channel is Searching from here
-                same::DevEvent inj{};
-                inj.channel = ncol; inj.kind = SAME_LINK_SEARCHING; inj.sample_counter = h;
-                inj.symbol_count = ts.a_sym + (uint64_t)((double)(h > ts.a_t ? h - ts.a_t : 0) / sps + 0.5);
-                inj.burst_slot = 0xffffffffu;
-                feed(part, ev, inj, c, 0);
-            }
-            cur = nxt;
-        }
-        // the remainder of the call (less than a block), demodulated on the channel's real state afterwards,
-        // logs under column c like chunk 0
-        for (uint32_t i = first[c]; i < first[c + 1u]; ++i)
-            if (evs[order[i]].sample_counter > sl.end_blocks) feed(part, ev, evs[order[i]], c, off);
-        rx->tp.sym_off[c] = off;
-    };
-    auto run_range = [&](uint32_t c0, uint32_t c1, Part &part) {
-        part.out.clear(); part.bytes.clear(); part.rearm.clear(); part.bursts.clear();
-        part.out.reserve((size_t)(cfirst[c1] - cfirst[c0]) * 3 / 2 + 4);
-        same_rx_event ev;                                  // (scratch for what the transport layer returns)
-        std::memset(&ev, 0, sizeof(ev));
-        for (uint32_t c = c0; c < c1; ++c) {
-            // (the next channel's transport state: its hot line is in the cache as a rule -- 2 MB for 32 768 channels -- the burst
-            // history and message texts are not: all of them when a burst is on its way there)
-            if (!link_only && c + 1u < c1) {
-                __builtin_prefetch(&rx->thot[c + 1u]);
-                if (!sl.chunked) {
-                    bool burst = false;
-                    for (uint32_t k = first[c + 1u]; k < first[c + 2u]; ++k) burst |= evs[k].kind == SAME_LINK_BURST;
-                    const char *nx = reinterpret_cast<const char *>(&rx->tcold[c + 1u]);
-                    if (burst) for (size_t o = 0; o < sizeof(same::TransportCold); o += 64) __builtin_prefetch(nx + o);
-                }
-            }
-            // this channel's column ranges back into log order (see above)
-            { HP(0);
-            for (uint32_t col = c; col < n_bins; col += n_ch)
-                if (first[col + 1u] - first[col] > 1u)
-                    std::sort(evs_mut + first[col], evs_mut + first[col + 1u],
-                              [](const same::DevEvent &a, const same::DevEvent &b) { return a.channel < b.channel; });
-            }
-            if (sl.chunked) stitch(part, ev, c);
-            else
-                for (uint32_t k = first[c]; k < first[c + 1u]; ++k)
-                    feed(part, ev, evs[order[k]], c, tp ? rx->tp.sym_off[c] : 0);
-            if (tp && !link_only) {
-                // polls due before the end of this launch (the next launch's events start after it)
-                TickSynth &ts = rx->tp.synth[c];
-                if (ts.link == SAME_LINK_NO_CARRIER && sl.end_counter > ts.a_t) {
-                    const uint64_t sym_end = ts.a_sym + (uint64_t)((double)(sl.end_counter - ts.a_t) / sps);
-                    auto poll = [&](uint64_t psym, uint64_t pt) {
-                        if (rx->tr(c).on_link_event(same::kDevTick, pt, psym, nullptr, 0, rx->P.input_rate, &ev)) push_transport(part, ev, c);
-                    };
-                    ts.run_until(sym_end + 1u, sl.end_counter + 1u, sps, rx->tr(c).force_eom_at(), poll);
-                }
-            }
-        }
-    };
-    uint32_t n_threads = 1;
-    if (n_real >= 16384u && n_ch >= 64u) {
-        const unsigned hw = std::thread::hardware_concurrency();
-        // up to 32 replay threads, at most an eighth of the host's hardware threads (eight ranks share a node)
-        n_threads = std::min<uint32_t>({32u, std::max(16u, hw / 8u), hw ? hw : 1u, n_ch / 32u});
-        // (Measured against the container's cgroup CPU quota in round 5 -- the GPU boxes give 16 CPUs of 256 visible: capping the
-        // pool at the quota made the headline step host-bound (replay 1.3-1.6 ms on 16 threads, 2.17 ms per step) where 32 threads
-        // finish it in 0.8 ms and 2.09 ms per step; a burst of 32 threads for under a millisecond per 2 ms step stays inside a
-        // 16-CPU quota on average and is not throttled.)
-        if (rx->host_threads > 0) n_threads = (uint32_t)rx->host_threads;
-    }
-    if (rx->parts.size() < n_threads) rx->parts.resize(n_threads);
-    std::vector<Part> &parts = rx->parts;
-    for (Part &p : parts) { p.out.clear(); p.bytes.clear(); p.rearm.clear(); p.bursts.clear(); }
-    if (n_threads == 1) {
-        run_range(0, n_ch, parts[0]);
-    } else {
-        // split by event count, on channel boundaries
-        std::vector<uint32_t> cut(n_threads + 1u, n_ch);
-        cut[0] = 0;
-        for (uint32_t t = 1; t < n_threads; ++t) {
-            const uint32_t target = (uint32_t)((uint64_t)n_real * t / n_threads);
-            cut[t] = (uint32_t)(std::lower_bound(cfirst.begin(), cfirst.end(), target) - cfirst.begin());
-            cut[t] = std::min(std::max(cut[t], cut[t - 1u]), n_ch);
-        }
-        rx->workers.run(n_threads, [&](size_t t) { run_range(cut[t], cut[t + 1u], parts[t]); });
-    }
-    times.replayed = std::chrono::steady_clock::now();
-    times.n_threads = n_threads;
-    size_t total = 0, total_bytes = 0;
-    for (const Part &p : parts) { total += p.out.size(); total_bytes += p.bytes.size(); }
-    prepare_queue_append(rx);
-    QEvent *dst = rx->queue.grow(total);
-    if (total && !dst) return fail(SAME_ENOMEM, "event queue");
-    uint8_t *bdst = rx->arena.grow(total_bytes);
-    if (total_bytes && !bdst) return fail(SAME_ENOMEM, "event payloads");
-    {
-        // every thread's slice lands at its prefix offset; the copies run side by side
-        size_t at = 0, bat = 0;
-        if (rx->burst_seq_head > 4096 && rx->burst_seq_head * 2 > rx->burst_seq.size()) {
-            rx->burst_seq.erase(rx->burst_seq.begin(), rx->burst_seq.begin() + (std::ptrdiff_t)rx->burst_seq_head);
-            rx->burst_seq_head = 0;
-        }
-        const size_t seq0 = rx->queue.base + (size_t)(dst - rx->queue.data());
-        const size_t byte0 = rx->arena.base + (size_t)(bdst - rx->arena.data());
-        struct Job { QEvent *q; uint8_t *b; Part *p; size_t byte_off; };
-        std::vector<Job> jobs;
-        for (size_t t = 0; t < parts.size(); ++t) {
-            Part &p = parts[t];
-            if (p.out.empty()) continue;
-            for (uint32_t i : p.bursts) rx->burst_seq.push_back(seq0 + at + i);
-            jobs.push_back(Job{dst + at, bdst + bat, &p, byte0 + bat});
-            at += p.out.size(); bat += p.bytes.size();
-        }
-        rx->workers.run(jobs.size(), [&](size_t j) {
-            const Job &job = jobs[j];
-            for (QEvent &q : job.p->out) q.payload += job.byte_off;            // part-relative -> absolute
-            std::memcpy(job.q, job.p->out.data(), job.p->out.size() * sizeof(QEvent));
-            if (!job.p->bytes.empty()) std::memcpy(job.b, job.p->bytes.data(), job.p->bytes.size());
-        });
-    }
-    for (Part &p : parts) rearm.insert(rearm.end(), p.rearm.begin(), p.rearm.end());
-    return SAME_OK;
-}
-
-// ---- a harvest on file (tools/host_step_probe.py --ranks N: the host half of a step without a device) ----------------
-// SAME_RECORD_HARVEST=<path>: the third harvest of a batch writes what the host half reads -- the ordered log, the columns'
-// offsets, the burst pool, hand-over instants and chunk geometry -- to <path>.
-struct HarvestFileHeader {
-    uint64_t magic;                  // "SAMEHRV1"
-    uint32_t n_channels, n_bins, n_events, n_bursts, chunked, per_channel, flags, input_rate, tp_enabled, pad;
-    same::ChunkGeom geom;
-    uint64_t end_blocks, end_counter;
-};
-constexpr uint64_t kHarvestMagic = 0x3156524845'4d4153ull;
-int record_harvest(same_batch *rx, same_batch::Slot &sl, uint32_t n_events, uint32_t n_bursts, const char *path)
+// SAME_RECORD_HARVEST=<path>: the third harvest of a batch writes what the host half reads to <path> (same_harvest.h)
+int record_harvest(same_batch *rx, same_batch::Slot &sl, const same::HarvestInput &in, uint32_t n_events, uint32_t n_bursts, const char *path)
 {
     if (sl.seq != 3u) return SAME_OK;
-    std::FILE *f = std::fopen(path, "wb");
-    if (!f) return fail(SAME_EINVAL, "SAME_RECORD_HARVEST: cannot write %s", path);
     const uint32_t n_ch = rx->P.n_channels, n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;
-    HarvestFileHeader h{};
-    h.magic = kHarvestMagic;
+    same::HarvestFileHeader h{};
     h.n_channels = n_ch; h.n_bins = n_bins; h.n_events = n_events; h.n_bursts = n_bursts;
     h.chunked = sl.chunked; h.per_channel = sl.per_channel; h.flags = rx->flags; h.input_rate = rx->P.input_rate; h.tp_enabled = rx->tp.enabled;
     h.geom = sl.geom; h.end_blocks = sl.end_blocks; h.end_counter = sl.end_counter;
-    bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1;
-    ok = ok && std::fwrite(sl.h_sort, sizeof(uint32_t), (size_t)n_bins + 1, f) == (size_t)n_bins + 1;
-    ok = ok && (!n_events || std::fwrite(sl.h_events, sizeof(same::DevEvent), n_events, f) == n_events);
-    ok = ok && (!n_bursts || std::fwrite(sl.h_bursts, same::kBurstCap, n_bursts, f) == n_bursts);
-    if (sl.chunked) {
-        ok = ok && std::fwrite(sl.h_handover, sizeof(uint64_t), n_bins, f) == n_bins;
-        if (sl.per_channel) ok = ok && std::fwrite(sl.h_geom, sizeof(uint32_t), (size_t)2 * n_bins, f) == (size_t)2 * n_bins;
-    }
-    std::fclose(f);
-    return ok ? SAME_OK : fail(SAME_EINVAL, "SAME_RECORD_HARVEST: short write to %s", path);
+    return same::write_harvest_file(path, h, in);
 }
 
 // a pinned landing buffer of at least `need` bytes
 hipError_t grow_pinned(same::PinnedBuf<void> &b, size_t need)
 {
     return need <= b.size() ? hipSuccess : b.ensure(need + need / 2 + 4096);
-}
-
-// Before chunks are appended to the audio queue: reclaim the dropped prefix once it is at least as large as what is still queued
-// (the queue and the sample arena move: a view of same_batch_peek_audio is stale by then anyway)
-AudioChunk *audio_grow(same_batch *rx, size_t n_chunks, size_t n_samples, float **samples_at, uint64_t *at)
-{
-    same_batch::Audio &A = rx->audio;
-    if (A.head && A.head >= A.queue.size() - A.head) {
-        A.head = A.queue.compact(A.head);
-        const uint64_t keep_from = A.queue.size() ? A.queue.data()[0].at : A.samples.base + A.samples.size();
-        A.samples.compact((size_t)(keep_from - A.samples.base));
-    }
-    AudioChunk *dst = A.queue.grow(n_chunks);
-    if (n_chunks && !dst) return nullptr;
-    float *sdst = A.samples.grow(n_samples);
-    if (n_samples && !sdst) { A.queue.n -= n_chunks; return nullptr; }
-    *samples_at = sdst;
-    *at = A.samples.base + (A.samples.size() - n_samples);
-    return dst;
-}
-
-// The channels' open captures end at a reset (same_batch_reset_channels) at batch position `pos`: an empty END_RESET chunk at the
-// counter the capture had reached.  Called once every chunk before `pos` is queued, before the channels' counter bases move.
-int audio_end_reset(same_batch *rx, const std::vector<uint32_t> &chans, uint64_t pos)
-{
-    same_batch::Audio &A = rx->audio;
-    if (!A.per_launch) return SAME_OK;
-    size_t n = 0;
-    for (uint32_t c : chans) n += A.open[c];
-    if (!n) return SAME_OK;
-    float *sdst = nullptr;
-    uint64_t at = 0;
-    AudioChunk *dst = audio_grow(rx, n, 0, &sdst, &at);
-    if (!dst) return fail(SAME_ENOMEM, "audio queue");
-    for (uint32_t c : chans) {
-        if (!A.open[c]) continue;
-        *dst++ = AudioChunk{c, SAME_AUDIO_END_RESET, rx->resets.rebase(c, pos), 0, at};
-        A.open[c] = 0;
-    }
-    return SAME_OK;
 }
 
 // The audio of a launch that captured (same_capture.hip): the spans and the used part of the pool come back on the copy stream
@@ -999,27 +422,8 @@ int harvest_audio(same_batch *rx, same_batch::Slot &sl)
     HIP_TRY(hipStreamSynchronize(rx->copy_stream));
     const same::cap::Span *sp = static_cast<const same::cap::Span *>(sl.h_spans.get());
     const float *pool = static_cast<const float *>(sl.h_pool.get());
-    std::vector<uint32_t> order(n_spans);
     size_t n_samples = 0;
-    for (uint32_t i = 0; i < n_spans; ++i) {
-        order[i] = i;
-        if (sp[i].n && sp[i].off + sp[i].n <= used) n_samples += sp[i].n;
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sp[a].channel != sp[b].channel ? sp[a].channel < sp[b].channel : a < b; });
-    float *sdst = nullptr;
-    uint64_t at = 0;
-    AudioChunk *dst = audio_grow(rx, n_spans, n_samples, &sdst, &at);
-    if (!dst) return fail(SAME_ENOMEM, "audio queue");
-    for (uint32_t k = 0; k < n_spans; ++k) {
-        const same::cap::Span &s = sp[order[k]];
-        const uint32_t n = s.n && s.off + s.n <= used ? s.n : 0;
-        uint32_t flags = s.flags;
-        if (n < s.n) flags |= SAME_AUDIO_TRUNCATED;
-        dst[k] = AudioChunk{s.channel, flags, rx->resets.rebase(s.channel, s.counter), n, at};
-        if (n) { std::memcpy(sdst, pool + s.off, (size_t)n * sizeof(float)); sdst += n; at += n; }
-        if (flags & SAME_AUDIO_FIRST) A.open[s.channel] = 1;
-        if (flags & (SAME_AUDIO_END_MESSAGE | SAME_AUDIO_END_FLUSH | SAME_AUDIO_END_RESET)) A.open[s.channel] = 0;
-    }
+    if (const int arc = A.log.append_spans(sp, n_spans, pool, used, rx->resets, &n_samples)) return arc;
     if (rx->debug)
         std::fprintf(stderr, "[same] audio: %u chunks, %zu samples (pool %zu of %zu)%s\n", n_spans, n_samples, used, A.per_launch,
                      cur.overflow ? ", truncated" : "");
@@ -1042,36 +446,7 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
     }
     auto t_copied = std::chrono::steady_clock::now();
     const same::DevMessage *far = static_cast<const same::DevMessage *>(sl.h_msgs.get());
-    auto rec = [&](uint32_t i) -> const same::DevMessage & { return i < n_near ? sl.h_near[i] : far[i - n_near]; };
-    std::vector<uint32_t> order(n_msgs);
-    size_t n_bytes = 0;
-    for (uint32_t i = 0; i < n_msgs; ++i) {
-        order[i] = i;
-        if (rec(i).kind == SAME_TRANSPORT_MSG_START) n_bytes += std::min<uint32_t>(rec(i).len, same::kDevMessageText);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        const same::DevMessage &x = rec(a), &y = rec(b);
-        return x.channel != y.channel ? x.channel < y.channel : x.seq < y.seq;
-    });
-    prepare_queue_append(rx);
-    QEvent *dst = rx->queue.grow(n_msgs);
-    if (n_msgs && !dst) return fail(SAME_ENOMEM, "event queue");
-    uint8_t *bdst = rx->arena.grow(n_bytes);
-    if (n_bytes && !bdst) return fail(SAME_ENOMEM, "event payloads");
-    size_t at = n_bytes ? rx->arena.base + (size_t)(bdst - rx->arena.data()) : 0;
-    for (uint32_t k = 0; k < n_msgs; ++k) {
-        const same::DevMessage &d = rec(order[k]);
-        QEvent q{};
-        q.kind = d.kind; q.channel = d.channel; q.sample_counter = rx->resets.rebase(d.channel, d.sample_counter);
-        q.symbol_count = d.symbol_count; q.len = d.len; q.aux = d.aux; q.aux2 = d.aux2;
-        if (d.kind == SAME_TRANSPORT_MSG_START && d.len) {
-            q.n_bytes = std::min<uint32_t>(d.len, same::kDevMessageText);
-            q.payload = at;
-            std::memcpy(bdst, d.text, q.n_bytes);
-            bdst += q.n_bytes; at += q.n_bytes;
-        }
-        dst[k] = q;
-    }
+    if (const int mrc = rx->replay.append_messages(sl.h_near.get(), n_near, far, n_far)) return mrc;
     if (sl.captured) {
         const int arc = harvest_audio(rx, sl);
         if (arc) return arc;
@@ -1082,7 +457,7 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
     rx->resets.done_shift(si);
     // the harvest has reached the resets asked for behind this launch: their host half (the counter bases) is due
     // (the open captures of the channels end there, in their counters before the reset)
-    if (const int arc = audio_end_reset(rx, rx->resets.slot[si & 1].channels, rx->resets.rec_pos(si))) return arc;
+    if (const int arc = rx->audio.log.end_reset(rx->resets.slot[si & 1].channels, rx->resets.rec_pos(si), rx->resets)) return arc;
     for (uint32_t c : rx->resets.host_due(si)) reset_channel_host(rx, c, rx->resets.rec_pos(si));
     rx->resets.done_host(si);
     if (rx->debug) {
@@ -1165,21 +540,24 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     }
     if (n_bursts || sl.chunked) HIP_TRY(hipStreamSynchronize(rx->copy_stream));      // bursts, hand-overs, geometry
     auto t_copied = std::chrono::steady_clock::now();
-    if (!rx->record_path.empty()) { const int rrc = record_harvest(rx, sl, n_events, n_bursts, rx->record_path.c_str()); if (rrc != SAME_OK) return rrc; }
+    const same::HarvestInput in{sl.h_sort, static_cast<same::DevEvent *>(sl.h_events.get()), static_cast<const uint8_t *>(sl.h_bursts.get()),
+                                sl.h_handover, sl.h_geom};
+    if (!rx->record_path.empty()) { const int rrc = record_harvest(rx, sl, in, n_events, n_bursts, rx->record_path.c_str()); if (rrc != SAME_OK) return rrc; }
     std::vector<uint32_t> rearm;     // channels whose forced-EOM instant changed
-    HarvestTimes times;
-    const HarvestInput in{sl.h_sort, static_cast<same::DevEvent *>(sl.h_events.get()), static_cast<const uint8_t *>(sl.h_bursts.get()),
-                          sl.h_handover, sl.h_geom};
-    int rc = harvest_host(rx, sl, in, n_events, n_bursts, rearm, times);
+    same::HarvestTimes times;
+    same::HarvestLaunch launch;
+    launch.chunked = sl.chunked; launch.per_channel = sl.per_channel; launch.geom = sl.geom;
+    launch.end_blocks = sl.end_blocks; launch.end_counter = sl.end_counter;
+    int rc = rx->replay.replay(launch, in, n_events, n_bursts, rearm, times);
     if (rc) return rc;
     // a ragged launch's counter shifts are due now that its own events are replayed: the channels' armed forced-EOM instants
     // move with them (and are re-armed), then the queued records' counter bases
     {
         const int si = (int)(&sl - rx->slot);
         const same::ResetLedger::SlotShift &sh = rx->resets.shift_due(si);
-        if (!rx->thot.empty())
+        if (!rx->replay.thot.empty())
             for (size_t i = 0; i < sh.channels.size(); ++i)
-                if (rx->tr(sh.channels[i]).shift_force_eom(sh.by[i])) rearm.push_back(sh.channels[i]);
+                if (rx->replay.tr(sh.channels[i]).shift_force_eom(sh.by[i])) rearm.push_back(sh.channels[i]);
         rx->resets.done_shift(si);
     }
     // the harvest has reached the resets asked for behind this launch: their host half is due (before the wake table is
@@ -1200,7 +578,7 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
             HIP_TRY(rx->h_wake.ensure(rx->P.n_channels));
             std::memset(rx->h_wake, 0, (size_t)rx->P.n_channels * sizeof(uint64_t));
         }
-        for (uint32_t c : rearm) rx->h_wake[c] = rx->tr(c).force_eom_at();
+        for (uint32_t c : rearm) rx->h_wake[c] = rx->replay.tr(c).force_eom_at();
         if (rx->wake_ordered) {
             int rc2 = upload_wake_ordered(rx, sl);
             if (rc2) return rc2;
@@ -2003,7 +1381,7 @@ int process_ragged_host(same_batch *rx, const SampleT *h_x, size_t n_rows, const
 // ------------------------------------------------------------------------------------
 extern "C" {
 
-const char *same_last_error(void) { return g_last_error.c_str(); }
+const char *same_last_error(void) { return same::last_error(); }
 
 #ifndef SAME_SOURCE_HASH
 #define SAME_SOURCE_HASH "unknown"
@@ -2101,8 +1479,10 @@ int same_batch_new(const same_rx_builder *b, uint32_t n_channels, int device, ui
     }
     TRY_OR_CLEAN(hipStreamSynchronize(rx->own_stream));
 #undef TRY_OR_CLEAN
-    if (!(flags & SAME_BATCH_LINK_ONLY) && !rx->dev_transport) { rx->thot.resize(n_channels); rx->tcold.resize(n_channels); }
-    if (rx->tp.enabled) { rx->tp.sym_off.assign(n_channels, 0); rx->tp.synth.assign(n_channels, TickSynth{}); }
+    rx->replay.link_only = (flags & SAME_BATCH_LINK_ONLY) != 0;
+    rx->replay.messages_only = rx->messages_only;
+    rx->replay.time_parallel = rx->tp.enabled;
+    rx->replay.init(n_channels, rx->P.input_rate, !(flags & SAME_BATCH_LINK_ONLY) && !rx->dev_transport);
     rx->resets.init(n_channels);
     *out = rx;
     return SAME_OK;
@@ -2133,22 +1513,14 @@ int same_batch_reset(same_batch *rx)
     HIP_TRY(hipStreamSynchronize(rx->own_stream));
     rx->counter = 0;
     rx->inv.fill = 0;                        // (samples that were waiting for their window are dropped with the rest of the state)
-    rx->queue.clear(); rx->queue_head = 0;   // event_queue.clear() receiver.rs:194
-    rx->arena.clear();
-    rx->peeked_valid = false; rx->peeked_release = false; rx->peeked_head = 0;
-    std::vector<same_rx_event>().swap(rx->peeked);
-    rx->burst_seq.clear(); rx->burst_seq_head = 0;
-    for (uint32_t c = 0; c < (uint32_t)rx->thot.size(); ++c) rx->tr(c).reset();
-    for (auto &o : rx->tp.sym_off) o = 0;
-    for (auto &t : rx->tp.synth) t.reset();
+    rx->events.clear();                      // event_queue.clear() receiver.rs:194
+    rx->replay.reset();
     if (rx->h_wake) std::memset(rx->h_wake, 0, (size_t)rx->P.n_channels * sizeof(uint64_t));
     rx->resets.clear();                      // (per-channel resets still due are covered: every column was re-initialised)
     rx->overflowed = false;
     rx->kernel_fault = false;
     // the audio queue goes with the event queue, and every capture is closed (the reset kernel closed the device's records)
-    rx->audio.queue.clear(); rx->audio.head = 0; rx->audio.samples.clear();
-    std::vector<same_audio_chunk>().swap(rx->audio.view);
-    std::fill(rx->audio.open.begin(), rx->audio.open.end(), 0);
+    rx->audio.log.clear();
     rx->audio.flush_at = UINT64_MAX;
     return SAME_OK;
 }
@@ -2174,7 +1546,7 @@ int same_batch_reset_channels(same_batch *rx, const uint32_t *channels, size_t n
         if (rx->slot[s].in_flight && (newest < 0 || rx->slot[s].seq > rx->slot[newest].seq)) newest = s;
     if (newest < 0) {
         // every launch before the position is harvested: the open captures end here (in the counters before the reset)
-        const int arc = audio_end_reset(rx, rx->reset_list, rx->counter);
+        const int arc = rx->audio.log.end_reset(rx->reset_list, rx->counter, rx->resets);
         if (arc) return arc;
     }
     rx->resets.request(rx->reset_list, rx->counter, newest, rx->reset_now);
@@ -2275,98 +1647,25 @@ size_t same_batch_pending_events(same_batch *rx)
 {
     // events already brought back to the host; does not wait for launches still in flight
     if (!rx) return 0;
-    return rx->queue.size() - rx->queue_head;
-}
-
-// The view same_batch_peek_events handed out is tens of MB for a large queue and is not kept for the handle's life -- but the
-// header promises it stays readable across same_batch_drop_events, so a drop that empties the queue only marks it; the next
-// call that ends the view's life anyway (poll, peek, a harvest, reset) lets the memory go.
-static void release_stale_view(same_batch *rx)
-{
-    if (!rx->peeked_release) return;
-    rx->peeked_release = false;
-    if (!rx->peeked_valid) std::vector<same_rx_event>().swap(rx->peeked);
-}
-// the queue is empty: nothing refers to the arena any more
-static void queue_emptied(same_batch *rx, bool view_may_be_read = false)
-{
-    rx->queue.clear(); rx->queue_head = 0; rx->arena.clear();
-    rx->peeked_valid = false; rx->peeked_head = 0;
-    if (view_may_be_read) rx->peeked_release = true;
-    else { rx->peeked_release = false; std::vector<same_rx_event>().swap(rx->peeked); }
+    return rx->events.pending();
 }
 
 int same_batch_poll_events(same_batch *rx, same_rx_event *out, size_t cap, size_t *n_out, size_t *n_left)
 {
     if (!rx || (!out && cap)) return fail(SAME_EINVAL, "null argument");
-    release_stale_view(rx);
-    const size_t avail = rx->queue.size() - rx->queue_head;
-    const size_t n = std::min(cap, avail);
-    const QEvent *q = rx->queue.data() + rx->queue_head;
-    const uint8_t *arena = rx->arena.data();
-    const size_t abase = rx->arena.base;
-    if (n >= 4096) {
-        const unsigned hw = std::thread::hardware_concurrency();
-        const size_t n_threads = std::min<size_t>({8u, hw ? hw : 1u});
-        rx->workers.run(n_threads, [&](size_t t) {
-            for (size_t i = n * t / n_threads; i < n * (t + 1) / n_threads; ++i) materialise(q[i], arena, abase, out + i);
-        });
-    } else {
-        for (size_t i = 0; i < n; ++i) materialise(q[i], arena, abase, out + i);
-    }
-    rx->queue_head += n;
-    if (rx->queue_head == rx->queue.size()) queue_emptied(rx);
-    if (n_out) *n_out = n;
-    if (n_left) *n_left = rx->queue.size() - rx->queue_head;
-    return SAME_OK;
+    return rx->events.poll(rx->replay.workers, out, cap, n_out, n_left);
 }
 
 int same_batch_peek_events(same_batch *rx, const same_rx_event **events, size_t *n)
 {
     if (!rx || !events || !n) return fail(SAME_EINVAL, "null argument");
-    // (the queue holds compact records: the view is made here, and stays valid as the header promises -- until the next
-    // call on this handle other than same_batch_pending_events / same_batch_drop_events)
-    release_stale_view(rx);
-    const size_t avail = rx->queue.size() - rx->queue_head;
-    if (rx->peeked_valid && rx->peeked_head == rx->queue_head && rx->peeked.size() == avail) {     // (nothing was queued or dropped since)
-        *n = avail; *events = avail ? rx->peeked.data() : nullptr;
-        return SAME_OK;
-    }
-    if (rx->peeked_valid && rx->peeked_head <= rx->queue_head && rx->queue_head - rx->peeked_head <= rx->peeked.size() &&
-        rx->peeked.size() - (rx->queue_head - rx->peeked_head) == avail) {
-        // only drops since the last peek (the usual consumer: peek, keep a few, drop): the view moves up, nothing is rebuilt
-        rx->peeked.erase(rx->peeked.begin(), rx->peeked.begin() + (ptrdiff_t)(rx->queue_head - rx->peeked_head));
-        rx->peeked_head = rx->queue_head;
-        *n = avail; *events = avail ? rx->peeked.data() : nullptr;
-        return SAME_OK;
-    }
-    try { rx->peeked.resize(avail); } catch (...) { return fail(SAME_ENOMEM, "event view"); }
-    rx->peeked_valid = true; rx->peeked_head = rx->queue_head;
-    const QEvent *q = rx->queue.data() + rx->queue_head;
-    const uint8_t *arena = rx->arena.data();
-    const size_t abase = rx->arena.base;
-    same_rx_event *out = rx->peeked.data();
-    if (avail >= 4096) {
-        const unsigned hw = std::thread::hardware_concurrency();
-        const size_t n_threads = std::min<size_t>({8u, hw ? hw : 1u});
-        rx->workers.run(n_threads, [&](size_t t) {
-            for (size_t i = avail * t / n_threads; i < avail * (t + 1) / n_threads; ++i) materialise(q[i], arena, abase, out + i);
-        });
-    } else {
-        for (size_t i = 0; i < avail; ++i) materialise(q[i], arena, abase, out + i);
-    }
-    *n = avail;
-    *events = avail ? out : nullptr;
-    return SAME_OK;
+    return rx->events.peek(rx->replay.workers, events, n);
 }
 
 int same_batch_drop_events(same_batch *rx, size_t n)
 {
     if (!rx) return fail(SAME_EINVAL, "null argument");
-    if (n > rx->queue.size() - rx->queue_head) return fail(SAME_EINVAL, "more events than are queued");
-    rx->queue_head += n;
-    if (rx->queue_head == rx->queue.size()) queue_emptied(rx, /*view_may_be_read=*/true);
-    return SAME_OK;
+    return rx->events.drop(n);
 }
 
 int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
@@ -2383,7 +1682,7 @@ int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
         for (same_batch::Slot &sl : rx->slot) { (void)sl.d_pool.reset(); (void)sl.d_spans.reset(); }
         (void)A.d_rec.reset();
         A.per_launch = 0;
-        A.open.clear();
+        A.log.open.clear();
     };
     release();
     if (!samples_per_launch) return SAME_OK;
@@ -2403,7 +1702,7 @@ int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
     }
     if (A.d_rec.ensure(rx->P.n_channels) != hipSuccess) return oom("capture records");
     HIP_TRY(hipMemset(A.d_rec, 0, (size_t)rx->P.n_channels * sizeof(same::cap::Rec)));
-    A.open.assign(rx->P.n_channels, 0);
+    A.log.open.assign(rx->P.n_channels, 0);
     A.per_launch = samples_per_launch;
     return SAME_OK;
 }
@@ -2411,58 +1710,19 @@ int same_batch_set_audio_capture(same_batch *rx, size_t samples_per_launch)
 int same_batch_peek_audio(same_batch *rx, const same_audio_chunk **chunks, size_t *n)
 {
     if (!rx || !chunks || !n) return fail(SAME_EINVAL, "null argument");
-    same_batch::Audio &A = rx->audio;
-    const size_t avail = A.queue.size() - A.head;
-    try { A.view.resize(avail); } catch (...) { return fail(SAME_ENOMEM, "audio view"); }
-    const AudioChunk *q = A.queue.data() + A.head;
-    for (size_t i = 0; i < avail; ++i) {
-        same_audio_chunk &o = A.view[i];
-        o.channel = q[i].channel; o.flags = q[i].flags; o.sample_counter = q[i].sample_counter; o.n_samples = q[i].n;
-        o.samples = A.samples.data() + (size_t)(q[i].at - A.samples.base);
-    }
-    *n = avail;
-    *chunks = avail ? A.view.data() : nullptr;
-    return SAME_OK;
+    return rx->audio.log.peek(chunks, n);
 }
 
 int same_batch_drop_audio(same_batch *rx, size_t n)
 {
     if (!rx) return fail(SAME_EINVAL, "null argument");
-    if (n > rx->audio.queue.size() - rx->audio.head) return fail(SAME_EINVAL, "more chunks than are queued");
-    rx->audio.head += n;       // (the memory is reclaimed by the next harvest that queues chunks: a view may still be read)
-    return SAME_OK;
+    return rx->audio.log.drop(n);
 }
 
 int same_batch_pack_bursts(same_batch *rx, uint32_t first_channel, uint8_t *out, size_t cap, size_t *n_records)
 {
     if (!rx || !n_records) return fail(SAME_EINVAL, "null argument");
-    static_assert(SAME_BURST_RECORD_BYTES == 16 + SAME_EVENT_MAX_BYTES, "record layout");
-    // the queued bursts by the index the harvest keeps (no scan of the whole queue: bursts are a fifth of the events)
-    const size_t first_seq = rx->queue.base + rx->queue_head;
-    while (rx->burst_seq_head < rx->burst_seq.size() && rx->burst_seq[rx->burst_seq_head] < first_seq) ++rx->burst_seq_head;
-    const size_t n_b = rx->burst_seq.size() - rx->burst_seq_head;
-    const size_t *seq = rx->burst_seq.data() + rx->burst_seq_head;
-    const QEvent *q = rx->queue.data();
-    const size_t base = rx->queue.base;
-    const uint8_t *arena = rx->arena.data();
-    const size_t abase = rx->arena.base;
-    *n_records = n_b;
-    if (!out || !cap) return SAME_OK;
-    const size_t n_copy = std::min(n_b, cap);
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t n_threads = n_copy >= 8192 ? std::min<size_t>({8u, hw ? hw : 1u}) : 1u;
-    auto copy_slice = [&](size_t t) {
-        for (size_t i = n_copy * t / n_threads; i < n_copy * (t + 1) / n_threads; ++i) {
-            const QEvent &e = q[seq[i] - base];
-            uint8_t *r = out + i * SAME_BURST_RECORD_BYTES;
-            const uint32_t ch = e.channel + first_channel, len = e.n_bytes;
-            std::memcpy(r, &ch, 4); std::memcpy(r + 4, &e.sample_counter, 8); std::memcpy(r + 12, &len, 4);
-            if (len) std::memcpy(r + 16, arena + ((size_t)e.payload - abase), len);
-            std::memset(r + 16 + len, 0, SAME_EVENT_MAX_BYTES - len);
-        }
-    };
-    rx->workers.run(n_threads, copy_slice);
-    return SAME_OK;
+    return rx->events.pack_bursts(rx->replay.workers, first_channel, out, cap, n_records);
 }
 
 int same_batch_read_trace(same_batch *rx, uint32_t channel, same_symbol_trace *out, size_t cap, size_t *n_out)
@@ -2524,92 +1784,11 @@ const char *same_batch_kernel_name(const same_batch *rx)
     return rx ? same::family_name(rx->last_family, rx->P.block_len) : "";
 }
 
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------
 // single receiver with the reference's pull semantics
 // ------------------------------------------------------------------------------------
-
-// The host half of a step on a recorded launch, `reps` times on `threads` harvest threads, without a device: wall time of
-// each repetition in ms_out[reps] (the record's counters are moved on by the launch's length every time, so the transport
-// layer sees a stream that continues).  Returns the number of queue records one repetition produced, or a negative error.
-long same_debug_harvest_replay(const char *path, int threads, int reps, double *ms_out)
-{
-    if (!path || reps <= 0 || !ms_out) return -(long)fail(SAME_EINVAL, "null argument");
-    std::FILE *f = std::fopen(path, "rb");
-    if (!f) return -(long)fail(SAME_EINVAL, "cannot read %s", path);
-    HarvestFileHeader h{};
-    bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && h.magic == kHarvestMagic && h.n_bins >= h.n_channels && h.n_channels > 0;
-    std::vector<uint32_t> first, geom;
-    std::vector<same::DevEvent> ev0, ev;
-    std::vector<uint8_t> bursts;
-    std::vector<uint64_t> hand0, hand;
-    if (ok) {
-        first.resize((size_t)h.n_bins + 1); ev0.resize(h.n_events); bursts.resize((size_t)h.n_bursts * same::kBurstCap);
-        ok = std::fread(first.data(), sizeof(uint32_t), first.size(), f) == first.size();
-        ok = ok && (!h.n_events || std::fread(ev0.data(), sizeof(same::DevEvent), h.n_events, f) == h.n_events);
-        ok = ok && (!h.n_bursts || std::fread(bursts.data(), same::kBurstCap, h.n_bursts, f) == h.n_bursts);
-        if (ok && h.chunked) {
-            hand0.resize(h.n_bins);
-            ok = std::fread(hand0.data(), sizeof(uint64_t), h.n_bins, f) == h.n_bins;
-            if (ok && h.per_channel) { geom.resize((size_t)2 * h.n_bins); ok = std::fread(geom.data(), sizeof(uint32_t), geom.size(), f) == geom.size(); }
-        }
-    }
-    std::fclose(f);
-    if (ok) {
-        // a record is data from a file: nothing in it is trusted before it has been checked against the sizes that were read
-        ok = first[h.n_bins] <= h.n_events && h.n_bins % h.n_channels == 0;
-        for (size_t i = 0; ok && i < (size_t)h.n_bins; ++i) ok = first[i] <= first[i + 1];
-        for (size_t i = 0; ok && i < ev0.size(); ++i)
-            ok = (ev0[i].burst_slot == 0xffffffffu || ev0[i].burst_slot < h.n_bursts) && (ev0[i].kind == same::kDevEventNone || ev0[i].kind <= 8u);
-        if (ok && h.chunked) {
-            ok = h.geom.n_chunks >= 1 && (uint64_t)h.geom.n_chunks * h.n_channels == h.n_bins && h.geom.block_len >= 1 && h.geom.stride_blocks >= 1;
-            for (size_t i = 0; ok && h.per_channel && i < geom.size(); ++i) ok = geom[i] <= 0x7fffffffu;
-        } else if (ok) {
-            ok = h.n_bins == h.n_channels;
-        }
-    }
-    if (!ok) return -(long)fail(SAME_EINVAL, "%s is not a (consistent) harvest record", path);
-    same_batch *rx = new (std::nothrow) same_batch;
-    if (!rx) return -(long)fail(SAME_ENOMEM, "out of memory");
-    rx->P.n_channels = h.n_channels; rx->P.input_rate = h.input_rate; rx->flags = h.flags;
-    if (std::getenv("SAME_REPLAY_LINK_ONLY")) rx->flags |= SAME_BATCH_LINK_ONLY;      // (what the transport layer's share is)
-    rx->tp.enabled = h.tp_enabled != 0; rx->host_threads = threads;
-    if (!(h.flags & SAME_BATCH_LINK_ONLY)) { rx->thot.resize(h.n_channels); rx->tcold.resize(h.n_channels); }
-    if (rx->tp.enabled) { rx->tp.sym_off.assign(h.n_channels, 0); rx->tp.synth.assign(h.n_channels, TickSynth{}); }
-    rx->resets.init(h.n_channels);
-    same_batch::Slot &sl = rx->slot[0];
-    ev = ev0; hand = hand0;
-    const HarvestInput in{first.data(), ev.data(), bursts.data(), hand.data(), geom.data()};
-    sl.chunked = h.chunked != 0; sl.per_channel = h.per_channel != 0; sl.sort_bins = h.n_bins;
-    const uint64_t span = h.end_counter - h.geom.counter0;        // (an ordinary launch: geom is zero, the span the end counter -- fine for a stride)
-    const double sps = (double)h.input_rate / 520.83;
-    const uint64_t span_sym = (uint64_t)((double)span / sps);
-    long produced = 0;
-    int rc = SAME_OK;
-    for (int r = 0; r < reps && rc == SAME_OK; ++r) {
-        const uint64_t dt = span * (uint64_t)r, ds = span_sym * (uint64_t)r;
-        for (size_t i = 0; i < ev0.size(); ++i) { ev[i] = ev0[i]; ev[i].sample_counter += dt; if (!sl.chunked) ev[i].symbol_count += ds; }
-        for (size_t i = 0; i < hand0.size(); ++i) hand[i] = hand0[i] == same::kNoHandover ? hand0[i] : hand0[i] + dt;
-        sl.geom = h.geom; sl.geom.counter0 += dt;
-        sl.end_blocks = h.end_blocks + dt; sl.end_counter = h.end_counter + dt;
-        std::vector<uint32_t> rearm;
-        HarvestTimes times;
-        const auto t0 = std::chrono::steady_clock::now();
-        rc = harvest_host(rx, sl, in, h.n_events, h.n_bursts, rearm, times);
-        ms_out[r] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        produced = (long)(rx->queue.size() - rx->queue_head);
-        // the consumer's side: everything polled
-        rx->queue_head = rx->queue.size();
-        rx->burst_seq_head = rx->burst_seq.size();
-    }
-#ifdef SAME_HOST_PROF
-    { uint64_t tot = 0; for (int k = 0; k < 7; ++k) tot += g_hp[k];
-      for (int k = 0; k < 7; ++k) std::fprintf(stderr, "[same prof] %-24s %8.3f Mclk per harvest (%4.1f %% of the instrumented parts)\n", g_hp_name[k], (double)g_hp[k] / reps / 1e6, tot ? 100.0 * (double)g_hp[k] / (double)tot : 0.0); }
-#endif
-    delete rx;
-    return rc == SAME_OK ? produced : -(long)rc;
-}
-
-}  // extern "C"
 
 struct same_rx {
     same_batch *batch = nullptr;

@@ -4,7 +4,7 @@
 // The kernel runs behind launch_event_sort, on the launch's stream: the launch's event log is then in column order
 // (first[c] .. first[c + 1] of `sorted` are channel c's records, each `channel` field holding the record's index in the
 // log).  Inside a range the records stand in the order the scatter's atomics landed; the lane puts them back into log
-// order, which is the channel's time order, exactly as the host's replay does (same_batch.cpp harvest_host).
+// order, which is the channel's time order, exactly as the host's replay does (same_harvest.cpp Replay::replay).
 #include <hip/hip_runtime.h>
 
 #include "same_device.h"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The host half of a step (ordering, stitch, transport layer, queue: harvest_host in same_batch.cpp) without a device, on
+"""The host half of a step (ordering, stitch, transport layer, queue: Replay::replay in same_harvest.cpp) without a device, on
 recorded launches, in N processes side by side -- what N ranks of one node do to each other's harvest.
 
     python tools/host_step_probe.py --record DIR          (needs the GPU: writes DIR/harvest_<shape>.bin.xz)
