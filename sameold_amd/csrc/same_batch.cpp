@@ -877,16 +877,12 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
         size_t n_lock = n;
         if (rg) {
             const size_t row0 = (size_t)rg->row_off + done;
-            n_lock = rg->m > row0 ? std::min<size_t>(rg->m - row0, n) : 0;
             const uint32_t C = rx->P.n_channels;
             HIP_TRY(sl.h_counts.ensure(C));
             // (the slot's previous launch, the last reader of this buffer, has been harvested above)
             std::memcpy(sl.h_counts, rg->counts, (size_t)C * sizeof(uint32_t));
             rx->ragged_by.resize(C);
-            for (uint32_t c = 0; c < C; ++c) {
-                const size_t have = rg->counts[c] > row0 ? std::min<size_t>(rg->counts[c] - row0, n) : 0;
-                rx->ragged_by[c] = (uint32_t)(n - have);
-            }
+            n_lock = same::ragged_launch_split(rg->counts, C, rg->m, row0, n, rx->ragged_by.data());
         }
         same::ChunkGeom geom{};
         same::PipeChunks pc{};

@@ -126,5 +126,18 @@ struct ResetLedger {
     uint64_t rebase(uint32_t c, uint64_t device_counter) const { return device_counter > rec_base[c] ? device_counter - rec_base[c] : 0; }
 };
 
+// One launch of a ragged call: the launch covers the call's rows [row0, row0 + n), of which channel c consumes those below
+// counts[c] (m: the smallest count of the call).  Returns n_lock, the launch's rows that every channel consumes (its common
+// prefix), and writes by[c] = n - min(max(counts[c] - row0, 0), n), the rows channel c does not consume: what
+// ResetLedger::shift takes.  Over the launches that cover a call's rows [0, M) the by[c] sum to M - counts[c].
+inline size_t ragged_launch_split(const uint32_t *counts, uint32_t n_channels, uint32_t m, size_t row0, size_t n, uint32_t *by)
+{
+    for (uint32_t c = 0; c < n_channels; ++c) {
+        const size_t have = counts[c] > row0 ? std::min<size_t>(counts[c] - row0, n) : 0;
+        by[c] = (uint32_t)(n - have);
+    }
+    return m > row0 ? std::min<size_t>(m - row0, n) : 0;
+}
+
 }  // namespace same
 #endif  // SAME_RESETS_H

@@ -1,7 +1,10 @@
 """Ragged calls (same_batch_process_*_ragged), the parts that need no GPU: the four entry points are declared in
 include/same_rx.h with the prototypes the issue fixes, exported by the built library and declared by receiver.py; the counter
 shifts of ragged launches in the ledger (sameold_amd/csrc/same_resets.h) run a synthesised stream of launches, resets and
-harvests under ASan + UBSan against a per-channel model."""
+harvests under ASan + UBSan against a per-channel model; so does the per-launch arithmetic of a ragged call
+(same::ragged_launch_split, the function the batch host calls), over random calls cut into launches at random chunk limits --
+limits of 1 and limits beyond the call's largest count among them: every launch's common prefix and lags equal a row-by-row
+model's, the lags of a call's launches sum to M - counts[c], and every channel's counter base ends where the model puts it."""
 import ctypes as C
 import os
 import re
