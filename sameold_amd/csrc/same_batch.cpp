@@ -16,6 +16,7 @@
 #include <deque>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -26,9 +27,11 @@
 #include "same_hipmem.h"
 #include "same_launch.h"
 #include "same_resets.h"
+#include "same_tp_plan.h"
 #include "same_transport.h"
 
 using same::fail;        // (the one error channel: same_harvest.h)
+static_assert(sizeof(same::cap::Span) == same::kSpanBytes, "same_tp_plan.h sizes the span list");
 
 namespace {
 
@@ -81,12 +84,14 @@ struct same_batch {
         // time-parallel launch: geometry, the end of its last whole block, the hand-over instants
         bool chunked = false;
         same::ChunkGeom geom{};
+        uint32_t columns(uint32_t n_channels) const { return chunked ? geom.n_chunks * n_channels : n_channels; }      // state columns of the launch
         uint64_t end_blocks = 0;
         same::DevBuf<uint64_t> d_handover;
         same::PinnedBuf<uint64_t> h_handover;
         // per-channel chunk boundaries (channel-major input): device arrays of the launch, host copies for the stitch
         bool per_channel = false;
-        same::DevBuf<uint32_t> d_geom;       // [own_start | row0 | nominal | perm] x columns, then wg_blocks
+        same::TpGeomWords words;             // where each array lies in d_geom, and how much of it comes back
+        same::DevBuf<uint32_t> d_geom;
         same::PinnedBuf<uint32_t> h_geom;    // own_start | row0
         // channels re-initialised in front of this launch (same_batch_reset_channels): read in place by the reset kernel
         same::CoherentBuf<uint32_t> h_reset;
@@ -115,7 +120,7 @@ struct same_batch {
     // time-parallel mode (SAME_BATCH_TIME_PARALLEL)
     struct TimePar {
         bool enabled = false;
-        uint32_t max_chunks = 0, min_own = 0, warmup = 0;     // same_batch_time_parallel_config (0 = default)
+        same::TpConfig cfg;                                   // same_batch_time_parallel_config and the mode's knobs (same_tp_plan.h)
         uint32_t cap_columns = 0;                             // columns the wide state blob holds
         uint32_t carved_columns = 0;                          // columns Pv / Sv / the descriptor tables are laid out for
         int carved_family = -1;                               // ... and the kernel family Pv's knobs were set for
@@ -130,12 +135,9 @@ struct same_batch {
         same::DevBuf<float> d_energy;                       // scout scratch
         same::DevBuf<float> d_hist;                         // squelch histories by grid position (PipeChunks::hist_scratch)
         same::Event ev_plan_prev; bool plan_recorded = false;
-        int knob_plan_stream = 0;                            // SAME_TP_PLAN_STREAM=0: planning kernels stay on the launch stream (A/B measurements)
-        int sort_mode = -1;                                  // SAME_TP_SORT: -1 choose, 0 grid order, 1 pieces sorted by length into workgroups, 2 groups of 64 paired long with short
         uint32_t last_chunks = 1;
         bool last_per_channel = false;
-        same::Family family = same::Family::kPipe;            // which kernel runs the chunks of the call being planned (plan_chunks)
-        int knob_prologue = 0;                                // SAME_TP_PROLOGUE=0: init kernel, fill and cursor reset as separate launches (A/B measurements)
+        same::Family family = same::Family::kPipe;            // which kernel runs the chunks of the launch being queued (TpCut::choice)
     } tp;
     uint64_t launch_seq = 0;
     hipStream_t copy_stream = nullptr;   // read-back of finished launches, beside the compute stream
@@ -298,42 +300,27 @@ void read_knobs(same_batch *rx)
     rx->debug = rx->replay.debug = std::getenv("SAME_DEBUG") != nullptr;
     { const char *e = std::getenv("SAME_RECORD_HARVEST"); rx->record_path = e ? e : ""; }
     rx->replay.host_threads = std::max(0, num("SAME_HOST_THREADS", 0));
-    rx->tp.sort_mode = num("SAME_TP_SORT", -1);
-    rx->tp.knob_plan_stream = tri("SAME_TP_PLAN_STREAM");
-    rx->tp.knob_prologue = tri("SAME_TP_PROLOGUE");
+    rx->tp.cfg.sort_mode = num("SAME_TP_SORT", -1);
+    rx->tp.cfg.knob_plan_stream = tri("SAME_TP_PLAN_STREAM");
+    rx->tp.cfg.knob_prologue = tri("SAME_TP_PROLOGUE");
     rx->want.knob_relaxed = tri("SAME_RELAXED");
     { const char *e = std::getenv("SAME_RELAXED_KERNEL"); rx->P.knob_relaxed_kernel = !e ? 0 : (std::strcmp(e, "solo") == 0 ? 1 : (std::strcmp(e, "duo") == 0 ? 2 : 0)); }
     { const char *e = std::getenv("SAME_TP_KERNEL"); rx->want.knob_tp_kernel = !e ? 0 : (std::strcmp(e, "wave") == 0 ? 2 : (std::strcmp(e, "pipe") == 0 ? 1 : 0)); }
 }
 
+// the launch's output buffers, sized by output_caps (same_tp_plan.h); n_columns: the state columns of a time-parallel launch
 int ensure_output(same_batch *rx, same_batch::Slot &sl, size_t n_samples, same::Output &O, size_t n_columns = 0)
 {
-    const size_t n_ch = n_columns ? n_columns : rx->P.n_channels;
-    // Worst case per channel: an acquisition attempt (Searching ... NoCarrier) needs a
-    // fresh byte sync, i.e. at least 32 symbols, so < 2 link events per 32 symbols; bursts
-    // are rarer still.  Size generously: 4 events per 32 symbols + slack.
-    const double symbols = (double)n_samples * 520.83 / (double)rx->P.input_rate;
-    const size_t per_chan_events = (size_t)(symbols / 8.0) + 16;
-    const size_t per_chan_bursts = (size_t)(symbols / 160.0) + 4;   // a burst is >= 20 bytes
-    size_t ecap = std::min<size_t>(per_chan_events * n_ch, 0x7fffffffu / sizeof(same::DevEvent));
-    size_t bcap = std::min<size_t>(per_chan_bursts * n_ch, 0x7fffffffu / same::kBurstCap);
-    HIP_TRY(sl.d_events.ensure(ecap));
-    HIP_TRY(sl.d_bursts.ensure(bcap * same::kBurstCap));
-    if (rx->dev_transport && !n_columns) {
-        // a message needs a burst, except a pending one from an earlier launch and a forced end of message: two per channel more
-        HIP_TRY(sl.d_msgs.ensure(std::min<size_t>(bcap + 2 * n_ch, 0x7fffffffu / sizeof(same::DevMessage))));
-        // (a copy of a few kilobytes beside a launch that fills the machine waits for that launch: measured 2.7 ms at the
-        // 32 768-channel shard, the host spinning on it; writes into mapped memory need no copy)
-        if (!sl.h_near) HIP_TRY(sl.h_near.ensure(std::max<uint32_t>(4096u, (uint32_t)(n_ch / 4u))));
-        // a message ends at most one span, a channel's tail or flush adds one: spans past this are lost only when the
-        // message log overflows too
-        if (rx->audio.per_launch)
-            HIP_TRY(sl.d_spans.ensure(std::min<size_t>(n_ch + (size_t)sl.near_cap() + sl.msg_cap(), 0x7fffffffu / sizeof(same::cap::Span))));
-    }
+    const same::OutputCaps caps = same::output_caps(rx->P, n_samples, n_columns, rx->dev_transport, rx->audio.per_launch != 0, sl.near_cap(), sl.msg_cap());
+    HIP_TRY(sl.d_events.ensure(caps.events));
+    HIP_TRY(sl.d_bursts.ensure(caps.bursts * same::kBurstCap));
+    if (caps.messages) HIP_TRY(sl.d_msgs.ensure(caps.messages));
+    if (caps.near) HIP_TRY(sl.h_near.ensure(caps.near));
+    if (caps.spans) HIP_TRY(sl.d_spans.ensure(caps.spans));
     HIP_TRY(sl.d_sorted.ensure(sl.d_events.size()));
-    HIP_TRY(sl.d_sort.ensure(2 * n_ch + 1 + same::event_sort_extra_words((uint32_t)n_ch)));
-    HIP_TRY(sl.h_sort.ensure(n_ch + 1));
-    sl.sort_bins = (uint32_t)n_ch;
+    HIP_TRY(sl.d_sort.ensure(caps.sort_words));
+    HIP_TRY(sl.h_sort.ensure(caps.bins + 1));
+    sl.sort_bins = (uint32_t)caps.bins;
     O.events = sl.d_events; O.event_cap = sl.event_cap();
     O.bursts = sl.d_bursts; O.burst_cap = sl.burst_cap();
     O.n_events = sl.d_counters; O.n_bursts = sl.d_counters + 1; O.overflow = sl.d_counters + 2;
@@ -388,7 +375,7 @@ int launch_pending_resets(same_batch *rx, same_batch::Slot &sl, hipStream_t stre
 int record_harvest(same_batch *rx, same_batch::Slot &sl, const same::HarvestInput &in, uint32_t n_events, uint32_t n_bursts, const char *path)
 {
     if (sl.seq != 3u) return SAME_OK;
-    const uint32_t n_ch = rx->P.n_channels, n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;
+    const uint32_t n_ch = rx->P.n_channels, n_bins = sl.columns(n_ch);
     same::HarvestFileHeader h{};
     h.n_channels = n_ch; h.n_bins = n_bins; h.n_events = n_events; h.n_bursts = n_bursts;
     h.chunked = sl.chunked; h.per_channel = sl.per_channel; h.flags = rx->flags; h.input_rate = rx->P.input_rate; h.tp_enabled = rx->tp.enabled;
@@ -524,8 +511,7 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     HIP_TRY(grow_pinned(sl.h_bursts, bu_bytes));
     // the event log first: it is what the sort below needs, and the sort runs while the burst pool (the larger copy) and
     // the chunk geometry are still on their way
-    const uint32_t n_ch = rx->P.n_channels;
-    const uint32_t n_bins = sl.chunked ? sl.geom.n_chunks * n_ch : n_ch;     // state columns of the launch
+    const uint32_t n_bins = sl.columns(rx->P.n_channels);
     if (n_bins != sl.sort_bins) return fail(SAME_EINVAL, "internal: event sort made for %u columns, launch has %u", sl.sort_bins, n_bins);
     // (the log arrives ordered by column, with the columns' offsets: the device did that behind the launch; at most
     // n_events records are real, the exact count is the last offset)
@@ -536,7 +522,7 @@ int harvest_slot(same_batch *rx, same_batch::Slot &sl)
     if (sl.chunked) {
         HIP_TRY(hipMemcpyAsync(sl.h_handover, sl.d_handover, (size_t)n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, rx->copy_stream));
         if (sl.per_channel)
-            HIP_TRY(hipMemcpyAsync(sl.h_geom, sl.d_geom, (size_t)2 * n_bins * sizeof(uint32_t), hipMemcpyDeviceToHost, rx->copy_stream));
+            HIP_TRY(hipMemcpyAsync(sl.h_geom, sl.d_geom + sl.words.own_start, sl.words.harvest * sizeof(uint32_t), hipMemcpyDeviceToHost, rx->copy_stream));
     }
     if (n_bursts || sl.chunked) HIP_TRY(hipStreamSynchronize(rx->copy_stream));      // bursts, hand-overs, geometry
     auto t_copied = std::chrono::steady_clock::now();
@@ -612,45 +598,6 @@ int harvest(same_batch *rx)
     return SAME_OK;
 }
 
-// How a call of n samples is cut into time-parallel chunks: fills geom / pc and returns the number of
-// chunks, or 1 when the call runs as one strict launch (mode off, configuration without a pipeline kernel,
-// call too short).
-uint32_t plan_chunks(same_batch *rx, size_t n, same::ChunkGeom &geom, same::PipeChunks &pc, uint32_t column_cap = same::kTpColumnCap, bool channel_major = false)
-{
-    same_batch::TimePar &tp = rx->tp;
-    const uint32_t C = rx->P.n_channels;
-    const double sps = (double)rx->P.input_rate / 520.83;
-    auto fill = [&](uint32_t K, uint32_t fb) -> bool {
-        const uint32_t warm = tp.warmup ? tp.warmup : (uint32_t)(64.0 * sps + 0.5);
-        const uint32_t WB = (warm + fb - 1u) / fb;
-        const uint64_t TB = n / fb;
-        if (TB <= WB) return false;
-        const uint64_t SB = (TB - WB) / K;
-        const uint64_t min_own = tp.min_own ? tp.min_own : 4ull * WB * fb;
-        if (SB == 0 || SB * fb < min_own) return false;
-        geom.counter0 = rx->counter;
-        geom.n_chunks = K; geom.block_len = fb; geom.stride_blocks = (uint32_t)SB; geom.warmup_blocks = WB;
-        pc.n_chunks = K; pc.in_channels = C; pc.stride_blocks = (uint32_t)SB; pc.nominal_blocks = (uint32_t)SB + WB;
-        pc.handover = nullptr;
-        return true;
-    };
-    // the candidates, most pieces first (same_select.h: which batches are cut, into how many pieces at most, by which kernel)
-    const same::TpRule rule = same::tp_rule(rx->P, rx->mode, rx->want, tp.max_chunks, column_cap, channel_major);
-    for (uint32_t K = rule.k_max; K >= 2u; --K) {
-        same::Choice c;
-        if (same::tp_candidate(rx->P, rule, K, c) && fill(K, c.block_len)) { tp.family = c.family; return K; }
-    }
-    return 1;
-}
-
-// the hand-over records of a time-parallel launch: one per state column, device + pinned host copy
-int ensure_handover(same_batch::Slot &sl, uint32_t columns)
-{
-    HIP_TRY(sl.d_handover.ensure(columns));
-    HIP_TRY(sl.h_handover.ensure(columns));
-    return SAME_OK;
-}
-
 // the wide state blob: `columns` state columns laid out like the channel state, plus the copy tables
 int ensure_wide_state(same_batch *rx, uint32_t columns)
 {
@@ -711,8 +658,8 @@ struct RaggedLaunch {
 };
 
 // ---- The pieces every launch is made of.  process_time_major_launches and process_channel_major_native queue them in this order:
-// begin_launch, [tp_reserve, tp_start], the demodulation kernels, [tp_hand_back], [a sub-block tail], end_launch; what lies
-// between them -- the choice of kernel, the ragged remainder, the planning kernels and their stream -- is the caller's. ----
+// begin_launch, the demodulation kernels and a sub-block tail (a time-parallel launch, of either layout: launch_time_parallel),
+// end_launch; how the call is cut is same_tp_plan.h's, the ragged remainder the caller's. ----
 
 // The begin of a launch into `sl`: the slot's previous launch is collected (its buffers are about to be reused), the stream is
 // ordered behind the launch before this one, and the channel resets asked for since then go in front
@@ -733,18 +680,7 @@ int begin_timing(same_batch *rx, same_batch::Slot &sl, hipStream_t stream)
     return SAME_OK;
 }
 
-// A time-parallel launch of n samples as `columns` state columns: the wide state, the output and the
-// hand-over records it needs, before anything is queued
-int tp_reserve(same_batch *rx, same_batch::Slot &sl, uint32_t columns, size_t n, const same::PipeChunks &pc, uint32_t block_len, same::Output &O)
-{
-    int rc = ensure_wide_state(rx, columns);
-    if (rc) return rc;
-    rc = ensure_output(rx, sl, std::min<size_t>(n, 3 * (size_t)pc.nominal_blocks * block_len + 65536), O, columns);
-    if (rc) return rc;
-    return ensure_handover(sl, columns);
-}
-
-// ... and its start on the stream: fresh receivers in every column (with the hand-over records, the event sort's bins and the
+// The start of a time-parallel launch on the stream: fresh receivers in every column (with the hand-over records, the event sort's bins and the
 // launch cursors: one kernel, launch_tp_prologue), then the channels' own state into chunk 0's columns.
 // *sort_bins_empty: the prologue kernel has emptied the event sort's bins
 int tp_start(same_batch *rx, same_batch::Slot &sl, uint32_t columns, const char *layout, hipStream_t stream, bool *sort_bins_empty)
@@ -752,7 +688,7 @@ int tp_start(same_batch *rx, same_batch::Slot &sl, uint32_t columns, const char 
     same_batch::TimePar &tp = rx->tp;
     const uint32_t C = rx->P.n_channels;
     *sort_bins_empty = false;
-    if (tp.knob_prologue >= 0) {
+    if (tp.cfg.knob_prologue >= 0) {
         HIP_TRY(same::launch_tp_prologue(tp.blob, tp.blob_fresh, tp.fresh_bytes, sl.d_handover, sl.d_sort, columns, sl.d_counters, stream));
         *sort_bins_empty = sl.sort_bins == columns;
     } else {
@@ -762,20 +698,8 @@ int tp_start(same_batch *rx, same_batch::Slot &sl, uint32_t columns, const char 
         HIP_TRY(same::launch_fill_u64(sl.d_handover, columns, same::kNoHandover, stream));
     }
     if (rx->debug) std::fprintf(stderr, "[same] time-parallel launch: %u columns (%s), start-up: %s\n", columns, layout,
-                                tp.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
+                                tp.cfg.knob_prologue >= 0 ? "prologue kernel" : "separate launches");
     HIP_TRY(same::launch_copy_state_columns(tp.d_desc_in, tp.n_desc, C, columns, nullptr, C, stream));
-    return SAME_OK;
-}
-
-// The state hand-back of a time-parallel launch: the channel's state afterwards is that of the chunk which ran to the end of
-// the input (own_start: the per-channel boundaries of a channel-major launch, [n_chunks][channels]; null: the uniform cut)
-int tp_hand_back(same_batch *rx, same_batch::Slot &sl, const same::ChunkGeom &geom, const uint32_t *own_start, hipStream_t stream)
-{
-    same_batch::TimePar &tp = rx->tp;
-    const uint32_t C = rx->P.n_channels;
-    if (own_start) HIP_TRY(same::launch_chunk_final_column_pc(sl.d_handover, own_start, C, geom.n_chunks, rx->counter, tp.d_final_col, stream));
-    else HIP_TRY(same::launch_chunk_final_column(sl.d_handover, C, geom, tp.d_final_col, stream));
-    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_out, tp.n_desc, geom.n_chunks * C, C, tp.d_final_col, C, stream));
     return SAME_OK;
 }
 
@@ -799,6 +723,106 @@ int demod_tail_corner(same_batch *rx, const same::Output &O, const float *corner
     const hipError_t e = same::launch_transpose(staged, rows, C, (uint32_t)r, stream);
     if (e != hipSuccess) return fail(SAME_EHIP, "demod kernel launch failed: %s", hipGetErrorString(e));
     return demod_tail(rx, O, rows, r, counter0, stream);
+}
+
+// The planning kernels of a channel-major launch with per-channel boundaries: an energy scout and the boundary
+// planner fill the slot's geometry buffer (np.words) ahead of the demodulation kernel; pc gets the arrays that kernel reads
+int tp_plan_boundaries(same_batch *rx, same_batch::Slot &sl, const same::TpCut &cut, const same::TpNative &np, const float *d_x,
+                       hipStream_t stream, same::PipeChunks &pc)
+{
+    same_batch::TimePar &tp = rx->tp;
+    const same::TpGeomWords &w = np.words;
+    same::TpPlan plan{};
+    plan.channels = rx->P.n_channels; plan.n_chunks = cut.n_chunks; plan.block_len = cut.geom.block_len;
+    plan.warmup_samples = np.warmup_samples; plan.whole_samples = np.whole_samples; plan.in_samples = np.in_samples;
+    plan.scout_blocks = np.scout_blocks;
+    uint32_t *g = sl.d_geom;
+    // On the library's own stream the planning kernels go to the plan stream: they need the input (ordered by
+    // same_batch_order_after, which both streams honour) and this slot's geometry buffers (free since the harvest above),
+    // not the previous launch -- so they run beside its tail instead of after it (~0.25 ms of small kernels per call at
+    // configs[1]).  On a caller's stream everything stays in that stream's order.
+    const bool side = same::tp_plan_beside(tp.cfg, stream == rx->own_stream);
+    hipStream_t ps = side ? rx->plan_stream : stream;
+    // (the energy map is one buffer for both slots: this call's scout after the previous call's planner, whichever
+    // streams the two ran on)
+    if (tp.plan_recorded) HIP_TRY(hipStreamWaitEvent(ps, tp.ev_plan_prev, 0));
+    HIP_TRY(same::launch_tp_plan(d_x, plan, tp.d_energy, g + w.own_start, g + w.row0, g + w.nominal, g + w.perm, g + w.wg, np.sort_mode != 0, ps,
+                                 np.lpt ? g + w.perm2 : nullptr, np.lpt ? g + w.wg2 : nullptr, np.pair_groups));
+    HIP_TRY(tp.ev_plan_prev.ensure());
+    HIP_TRY(hipEventRecord(tp.ev_plan_prev, ps));
+    tp.plan_recorded = true;
+    if (side) {
+        HIP_TRY(hipEventRecord(sl.ev_planned, ps));
+        HIP_TRY(hipStreamWaitEvent(stream, sl.ev_planned, 0));
+    }
+    pc.col_row0 = g + w.row0; pc.col_nominal = g + w.nominal;
+    pc.wg_blocks = g + (np.lpt ? w.wg2 : w.wg); pc.col_perm = np.lpt ? g + w.perm2 : nullptr;
+    pc.in_samples = np.in_samples; pc.whole_samples = np.whole_samples;
+    pc.hist_scratch = np.need_hist ? tp.d_hist.get() : nullptr;
+    return SAME_OK;
+}
+
+// A time-parallel launch of the n_call samples at x, cut as `cut`: every channel as cut.n_chunks state columns
+// side by side.  np null: time-major rows, the uniform cut; else a channel-major input read where it lies, every column from
+// its own first row (tp_plan_boundaries).  Between the caller's begin_launch and end_launch.
+template <typename SampleT>
+int launch_time_parallel(same_batch *rx, same_batch::Slot &sl, hipStream_t stream, const same::TpCut &cut, const same::TpNative *np,
+                         const SampleT *x, size_t n_call, bool *sort_bins_empty)
+{
+    same_batch::TimePar &tp = rx->tp;
+    const same::ChunkGeom &geom = cut.geom;
+    const uint32_t C = rx->P.n_channels, columns = cut.n_chunks * C, fb = geom.block_len;
+    const uint32_t total_blocks = (uint32_t)(n_call / fb);
+    const size_t n_whole = (size_t)total_blocks * fb;
+    tp.family = cut.choice.family;
+    // the wide state, the output (a channel-major launch sizes it for its whole blocks) and the hand-over records, one per
+    // state column, before anything is queued
+    same::Output O{};
+    int rc = ensure_wide_state(rx, columns);
+    if (rc == SAME_OK) rc = ensure_output(rx, sl, same::tp_output_samples(np ? n_whole : n_call, cut.pc, fb), O, columns);
+    if (rc) return rc;
+    HIP_TRY(sl.d_handover.ensure(columns));
+    HIP_TRY(sl.h_handover.ensure(columns));
+    same::PipeChunks pc = cut.pc;
+    pc.handover = sl.d_handover;
+    if (np) {
+        HIP_TRY(sl.d_geom.ensure(np->words.total));
+        HIP_TRY(sl.h_geom.ensure(np->words.harvest));
+        HIP_TRY(tp.d_energy.ensure(np->energy_floats));
+        if (np->need_hist) HIP_TRY(tp.d_hist.ensure(np->hist_floats));
+        sl.words = np->words;
+    }
+    rc = begin_timing(rx, sl, stream);
+    if (rc) return rc;
+    const float *xf = nullptr;      // the input as the per-channel form reads it (np is null for an int16 call)
+    if constexpr (std::is_same_v<SampleT, float>) xf = x;
+    if (np && (rc = tp_plan_boundaries(rx, sl, cut, *np, xf, stream, pc)) != SAME_OK) return rc;
+    rc = tp_start(rx, sl, columns, np ? "channel-major" : "time-major", stream, sort_bins_empty);
+    if (rc) return rc;
+    // (a launch with planning kernels brackets the demodulation kernel alone as well)
+    sl.have_k = np && sl.timed;
+    if (sl.have_k) HIP_TRY(hipEventRecord(sl.ev_k0, stream));
+    const hipError_t e = launch_family(tp.family, tp.Pv, tp.Sv, O, rx->d_taps, x, total_blocks, rx->counter, stream, pc);
+    rx->last_family = tp.family;
+    if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
+    if (sl.have_k) HIP_TRY(hipEventRecord(sl.ev_k1, stream));
+    // The channels' state afterwards: that of the chunk the hand-over chain ends in, as the host's stitch follows it --
+    // the last chunk as a rule (its columns end with the input); an earlier one where a burst ran on to the end of the
+    // call without a hand-over (a forced cut on a channel that is never quiet: its events are the ones that are kept).
+    if (np) HIP_TRY(same::launch_chunk_final_column_pc(sl.d_handover, sl.d_geom + np->words.own_start, C, geom.n_chunks, rx->counter, tp.d_final_col, stream));
+    else HIP_TRY(same::launch_chunk_final_column(sl.d_handover, C, geom, tp.d_final_col, stream));
+    HIP_TRY(same::launch_copy_state_columns(tp.d_desc_out, tp.n_desc, columns, C, tp.d_final_col, C, stream));
+    // less than a block is left: on the channels' own state (channel-major: its [C][r] corner of the input)
+    if (n_whole < n_call) {
+        rc = np ? demod_tail_corner(rx, O, xf + n_whole, n_call, n_call - n_whole, rx->counter + n_whole, stream)
+                : demod_tail(rx, O, x + n_whole * C, n_call - n_whole, rx->counter + n_whole, stream);
+        if (rc) return rc;
+    }
+    sl.chunked = true; sl.per_channel = np != nullptr;
+    sl.geom = geom;
+    sl.end_blocks = rx->counter + n_whole;
+    tp.last_chunks = cut.n_chunks; tp.last_per_channel = sl.per_channel;
+    return SAME_OK;
 }
 
 // The end of a launch of n samples: the stop event, the event sort, the transport layer and the audio capture on the device
@@ -862,9 +886,7 @@ int end_launch(same_batch *rx, same_batch::Slot &sl, same_batch::Slot &prev, hip
 template <typename SampleT>
 int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_samples, hipStream_t stream, const Ragged *rg = nullptr)
 {
-    // keep one launch comfortably inside u32 sample indices and bounded output pools, and
-    // well under the 135 s forced-EOM timeout the host arms one launch late (harvest)
-    const size_t kMaxChunk = std::min<size_t>((size_t)1 << 22, (size_t)rx->P.input_rate * 45);
+    const size_t kMaxChunk = same::max_launch_samples(rx->P.input_rate);
     size_t done = 0;
     while (done < n_samples) {
         const size_t n = std::min(kMaxChunk, n_samples - done);
@@ -884,40 +906,15 @@ int process_time_major_launches(same_batch *rx, const SampleT *d_x, size_t n_sam
             rx->ragged_by.resize(C);
             n_lock = same::ragged_launch_split(rg->counts, C, rg->m, row0, n, rx->ragged_by.data());
         }
-        same::ChunkGeom geom{};
-        same::PipeChunks pc{};
-        const uint32_t n_chunks = rg ? 1u : plan_chunks(rx, n, geom, pc);
-        rx->tp.last_chunks = n_chunks;
+        const same::TpCut cut = rg ? same::TpCut{} : same::tp_uniform_cut(rx->P, rx->mode, rx->want, rx->tp.cfg, n, rx->counter);
+        rx->tp.last_chunks = cut.n_chunks;
         sl.have_k = false;
         bool sort_bins_empty = false;          // the launch's prologue kernel has emptied the event sort's bins
-        same::Output O{};
-        if (n_chunks > 1u) {
-            // Time-parallel launch: every channel as n_chunks state columns side by side.
-            const uint32_t C = rx->P.n_channels, columns = n_chunks * C;
-            const size_t fbk = geom.block_len;
-            rc = tp_reserve(rx, sl, columns, n, pc, geom.block_len, O);
+        if (cut.n_chunks > 1u) {
+            rc = launch_time_parallel(rx, sl, stream, cut, nullptr, d_x + done * rx->P.n_channels, n, &sort_bins_empty);
             if (rc) return rc;
-            pc.handover = sl.d_handover;
-            same_batch::TimePar &tp = rx->tp;
-            rc = begin_timing(rx, sl, stream);
-            if (rc) return rc;
-            rc = tp_start(rx, sl, columns, "time-major", stream, &sort_bins_empty);
-            if (rc) return rc;
-            const SampleT *xp = d_x + done * C;
-            const uint32_t total_blocks = (uint32_t)(n / fbk);
-            const hipError_t e = launch_family(tp.family, tp.Pv, tp.Sv, O, rx->d_taps, xp, total_blocks, rx->counter, stream, pc);
-            rx->last_family = tp.family;
-            if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
-            rc = tp_hand_back(rx, sl, geom, nullptr, stream);
-            if (rc) return rc;
-            // less than a block is left: on the channels' own state
-            const size_t n_whole = (size_t)total_blocks * fbk;
-            if (n_whole < n && (rc = demod_tail(rx, O, xp + n_whole * C, n - n_whole, rx->counter + n_whole, stream)) != SAME_OK) return rc;
-            sl.chunked = true; sl.per_channel = false;
-            sl.geom = geom;
-            sl.end_blocks = rx->counter + n_whole;
-            rx->tp.last_per_channel = false;
         } else {
+        same::Output O{};
         sl.chunked = false; sl.per_channel = false;
         rc = ensure_output(rx, sl, n, O);
         if (rc) return rc;
@@ -1077,122 +1074,29 @@ int process_time_major(same_batch *rx, const SampleT *d_x, size_t n_samples, hip
     return SAME_OK;
 }
 
-// Time-parallel launch over a CHANNEL-MAJOR input with chunk boundaries chosen per channel at idle instants
-// (DESIGN.md 4.6): an energy scout and the boundary planner run on the device ahead of the demodulation kernel, every
-// state column then reads its own contiguous stream from its own first row.  Returns 1 when the call was handled, 0
-// when it does not qualify (the caller then takes the transposing path), < 0 on error.
-int process_channel_major_native(same_batch *rx, const float *d_x, size_t n, hipStream_t stream)
+// Time-parallel launch over a CHANNEL-MAJOR input with chunk boundaries chosen per channel at idle instants.
+// Returns 1 when the call was handled, 0 when it does not qualify (same_tp_plan.h: tp_native_plan; the caller then takes the
+// transposing path), < 0 on error.  The lanes' own streams are read as f32: an int16 call never qualifies.
+template <typename SampleT>
+int process_channel_major_native(same_batch *rx, const SampleT *d_x, size_t n, hipStream_t stream)
 {
-    same_batch::TimePar &tp = rx->tp;
-    if (!tp.enabled || n > ((size_t)1 << 22)) return 0;
-    // 22.05 kHz only: per-lane input streams are read by the sample stage of the 64-channel pipeline forms and by the
-    // relaxed kernels; the 44.1 / 48 kHz pipeline reads its input on the DC wavefront, which takes time-major rows only
-    // (such a call is transposed on the device and cut uniformly)
-    if (rx->P.ntaps != 42u) return 0;
-    same::ChunkGeom geom{};
-    same::PipeChunks pc{};
-    // (how many state columns the call may become: tp_native_column_cap, with the measurements behind it)
-    const uint32_t n_chunks = plan_chunks(rx, n, geom, pc, same::tp_native_column_cap(rx->P, rx->mode, tp.max_chunks), true);
-    if (n_chunks < 2u) return 0;
-    const uint32_t C = rx->P.n_channels, columns = n_chunks * C, fb = geom.block_len;
-    const bool wave = tp.family == same::Family::kWaveRelaxed;
-    const same::Params Pv = same::wide_params(rx->P, columns, same::is_fastmath(tp.family), true);
-    // 16-byte loads from every lane's stream (the scout's too: 16-byte aligned base and pitch; the relaxed kernel reads
-    // 8 bytes at a time from even rows), full 64-column workgroups.  What is left of the call behind its last whole block
-    // (less than a block) goes through the any-configuration kernel on the channels' own state afterwards.
-    const size_t n_call = n;
-    n -= n % fb;
-    if (n_call % 4 != 0 || ((uintptr_t)d_x & 15u) != 0u || n < 64u * (size_t)same::tp_scout_block() || n / same::tp_scout_block() > 7000u || n_chunks > 63u || C % same::kWave != 0u) return 0;
-    if (wave ? fb % 2 != 0 : (fb % 4 != 0 || same::pipe_workgroup_channels(Pv) != (uint32_t)same::kWave)) return 0;
+    if constexpr (!std::is_same_v<SampleT, float>) return 0;
+    else {
+    if (!rx->tp.enabled) return 0;
+    const same::TpCut cut = same::tp_native_cut(rx->P, rx->mode, rx->want, rx->tp.cfg, n, rx->counter);
+    const same::TpNative np = same::tp_native_plan(rx->P, rx->tp.cfg, cut, n, (uintptr_t)d_x);
+    if (!np.qualifies) return 0;
     same_batch::Slot &sl = rx->slot[rx->launch_seq & 1];
     same_batch::Slot &prev = rx->slot[(rx->launch_seq & 1) ^ 1];
     int rc = begin_launch(rx, sl, prev, stream);
     if (rc) return rc;
-    same::Output O{};
-    rc = tp_reserve(rx, sl, columns, n, pc, fb, O);
-    if (rc) return rc;
-    HIP_TRY(sl.d_geom.ensure((size_t)5 * columns + 3 * (columns / same::kWave)));
-    HIP_TRY(sl.h_geom.ensure((size_t)2 * columns));
-    same::TpPlan plan{};
-    plan.channels = C; plan.n_chunks = n_chunks; plan.block_len = fb;
-    // Warm-up: a per-channel boundary lies in silence, so all a fresh receiver needs before the next burst begins is a
-    // full squelch history (32 symbols; the preamble that follows is 128): 40 symbols unless the caller set one
-    {
-        const double sps = (double)rx->P.input_rate / 520.83;
-        const uint32_t warm = tp.warmup ? tp.warmup : (uint32_t)(40.0 * sps + 0.5);
-        plan.warmup_samples = std::min(geom.warmup_blocks, (warm + fb - 1u) / fb) * fb;
-    }
-    plan.whole_samples = (uint32_t)n; plan.in_samples = n_call;
-    plan.scout_blocks = (uint32_t)(n / same::tp_scout_block());
-    HIP_TRY(tp.d_energy.ensure((size_t)C * plan.scout_blocks));
-    uint32_t *d_own = sl.d_geom, *d_row0 = sl.d_geom + columns, *d_nom = sl.d_geom + 2 * (size_t)columns,
-             *d_perm = sl.d_geom + 3 * (size_t)columns, *d_wg = sl.d_geom + 4 * (size_t)columns,
-             *d_wg2 = d_wg + columns / same::kWave, *d_perm2 = d_wg2 + 2 * (columns / same::kWave);      // (d_wg2: [2][workgroups])
-    // pieces sorted by length into workgroups only when the workgroups come in more than one round (the long ones first;
-    // SAME_TP_SORT=0 / 1 overrides).  Within one round neither the sorted order nor a long workgroup beside a short one on
-    // every CU pays (round 2).
-    // SAME_TP_SORT=2 (measurement knob): grid order inside the groups of 64 columns, the groups paired longest with shortest into
-    // the symbol-paced pipeline's two-group workgroups, so that a long group runs the second part of its launch alone on its CU
-    // (a step is ~12 % shorter there).  One launch by itself: demodulation kernel 1.746 -> 1.706 ms; launches back to back, the
-    // way the bench and a stream step: 1.695 -> 1.732 (the shorter tail hides less of the next call's planning) -- not the default.
-    const bool pair_groups = tp.sort_mode == 2 && tp.family == same::Family::kSym;
-    const int sort_mode = pair_groups ? 0 : (tp.sort_mode >= 0 ? (tp.sort_mode ? 1 : 0) : (same::tp_more_than_one_round(columns) ? 1 : 0));
-    rc = begin_timing(rx, sl, stream);
-    if (rc) return rc;
-    // (sorted: the workgroups once more, longest first whatever their group -- those that wait for a free CU are then the short ones)
-    const bool lpt = sort_mode != 0 || pair_groups;
-    // On the library's own stream the planning kernels go to the plan stream: they need the input (ordered by
-    // same_batch_order_after, which both streams honour) and this slot's geometry buffers (free since the harvest above),
-    // not the previous launch -- so they run beside its tail instead of after it (~0.25 ms of small kernels per call at
-    // configs[1]).  On a caller's stream everything stays in that stream's order.
-    const bool side = stream == rx->own_stream && tp.knob_plan_stream >= 0;
-    hipStream_t ps = side ? rx->plan_stream : stream;
-    // (the energy map is one buffer for both slots: this call's scout after the previous call's planner, whichever
-    // streams the two ran on)
-    if (tp.plan_recorded) HIP_TRY(hipStreamWaitEvent(ps, tp.ev_plan_prev, 0));
-    HIP_TRY(same::launch_tp_plan(d_x, plan, tp.d_energy, d_own, d_row0, d_nom, d_perm, d_wg, sort_mode != 0, ps,
-                                 lpt ? d_perm2 : nullptr, lpt ? d_wg2 : nullptr, pair_groups));
-    HIP_TRY(tp.ev_plan_prev.ensure());
-    HIP_TRY(hipEventRecord(tp.ev_plan_prev, ps));
-    tp.plan_recorded = true;
-    if (side) {
-        HIP_TRY(hipEventRecord(sl.ev_planned, ps));
-        HIP_TRY(hipStreamWaitEvent(stream, sl.ev_planned, 0));
-    }
-    if (lpt) { d_perm = d_perm2; d_wg = d_wg2; }
     bool sort_bins_empty = false;
-    rc = tp_start(rx, sl, columns, "channel-major", stream, &sort_bins_empty);
+    rc = launch_time_parallel(rx, sl, stream, cut, &np, d_x, n, &sort_bins_empty);
     if (rc) return rc;
-    pc.handover = sl.d_handover;
-    pc.col_row0 = d_row0; pc.col_nominal = d_nom; pc.wg_blocks = d_wg; pc.col_perm = (sort_mode != 0 || pair_groups) ? d_perm : nullptr;
-    pc.in_samples = n_call; pc.whole_samples = (uint32_t)n;
-    pc.hist_scratch = nullptr;
-    if (pc.col_perm && tp.family == same::Family::kSym) {
-        HIP_TRY(tp.d_hist.ensure((size_t)columns * same::kSquelchHist));
-        pc.hist_scratch = tp.d_hist;
-    }
-    sl.have_k = sl.timed;
-    if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_k0, stream));
-    const hipError_t e = launch_family(tp.family, tp.Pv, tp.Sv, O, rx->d_taps, d_x, (uint32_t)(n / fb), rx->counter, stream, pc);
-    rx->last_family = tp.family;
-    if (e != hipSuccess) return fail(SAME_EHIP, "time-parallel demod kernel launch failed: %s", hipGetErrorString(e));
-    if (sl.timed) HIP_TRY(hipEventRecord(sl.ev_k1, stream));
-    // The channels' state afterwards: that of the chunk the hand-over chain ends in, as the host's stitch follows it --
-    // the last chunk as a rule (its columns end with the input); an earlier one where a burst ran on to the end of the
-    // call without a hand-over (a forced cut on a channel that is never quiet: its events are the ones that are kept).
-    rc = tp_hand_back(rx, sl, geom, d_own, stream);
-    if (rc) return rc;
-    // less than a block is left: its [C][r] corner of the input, on the channels' own state
-    if (n < n_call && (rc = demod_tail_corner(rx, O, d_x + n, n_call, n_call - n, rx->counter + n, stream)) != SAME_OK) return rc;
-    sl.chunked = true; sl.per_channel = true;
-    sl.geom = geom;
-    sl.end_blocks = rx->counter + n;
-    tp.last_chunks = n_chunks; tp.last_per_channel = true;
-    rc = end_launch<float>(rx, sl, prev, stream, nullptr, n_call, sort_bins_empty);
+    rc = end_launch<float>(rx, sl, prev, stream, nullptr, n, sort_bins_empty);
     return rc ? rc : 1;
+    }
 }
-// (the lanes' own streams are read as f32: an int16 call never qualifies)
-int process_channel_major_native(same_batch *, const int16_t *, size_t, hipStream_t) { return 0; }
 
 // A channel-major input of n_rows rows (row pitch `pitch`) as time-major launches: slabs of time are transposed through the
 // staging buffers, and launch(rows, n, t0) takes each -- n time-major rows that begin at the input's row t0
@@ -1768,7 +1672,7 @@ int same_batch_time_parallel_config(same_batch *rx, uint32_t max_chunks, uint32_
 {
     if (!rx) return fail(SAME_EINVAL, "null handle");
     if (!rx->tp.enabled) return fail(SAME_EINVAL, "batch was not created with SAME_BATCH_TIME_PARALLEL");
-    rx->tp.max_chunks = max_chunks; rx->tp.min_own = min_own_samples; rx->tp.warmup = warmup_samples;
+    rx->tp.cfg.max_chunks = max_chunks; rx->tp.cfg.min_own = min_own_samples; rx->tp.cfg.warmup = warmup_samples;
     return SAME_OK;
 }
 uint32_t same_batch_time_parallel_chunks(const same_batch *rx) { return rx ? rx->tp.last_chunks : 0; }

@@ -20,6 +20,7 @@
 #include "same_dev_common.h"
 #include "same_device.h"
 #include "same_launch.h"
+#include "same_tp_plan.h"      // kScoutBlock, kScanThreads: the host sizes the energy map and the scan's totals with them
 
 namespace same {
 
@@ -413,7 +414,7 @@ __global__ void ev_hist_kernel(const DevEvent *__restrict__ ev, const uint32_t *
 // column) with the workgroups' totals set aside, then every workgroup adds the totals before it.  (One workgroup walking
 // contiguous stretches per thread -- 48 dependent, uncoalesced loads and as many stores each at 49 152 columns -- took
 // 111 us between two demodulation launches.)
-constexpr uint32_t kScanThreads = 1024;
+// (kScanThreads threads per workgroup: same_tp_plan.h, which sizes the scan's totals with it)
 __global__ __launch_bounds__(kScanThreads) void ev_scan_local_kernel(uint32_t n_bins, const uint32_t *__restrict__ cnt, uint32_t *__restrict__ first,
                                                                       uint32_t *__restrict__ tot)
 {
@@ -454,7 +455,6 @@ __global__ void ev_scatter_kernel(const DevEvent *__restrict__ ev, const uint32_
         sorted[pos] = e;
     }
 }
-uint32_t event_sort_extra_words(uint32_t n_bins) { return (n_bins + kScanThreads - 1u) / kScanThreads; }
 hipError_t launch_event_sort(const DevEvent *ev, const uint32_t *counters, uint32_t cap, uint32_t n_bins, uint32_t *cnt, uint32_t *first,
                              DevEvent *sorted, hipStream_t stream, bool cnt_is_zero)
 {
@@ -624,11 +624,7 @@ hipError_t launch_chunk_final_column_pc(const uint64_t *handover, const uint32_t
     return hipGetLastError();
 }
 // ---- per-channel chunk boundaries (channel-major input) ----------------------------------------------------------
-#ifndef SAME_SCOUT_BLOCK
-#define SAME_SCOUT_BLOCK 256
-#endif
-constexpr uint32_t kScoutBlock = SAME_SCOUT_BLOCK;        // samples per energy reading (one 64-byte sector of them is read)
-uint32_t tp_scout_block() { return kScoutBlock; }
+// (kScoutBlock samples per energy reading, one 64-byte sector of them read: same_tp_plan.h; SAME_SCOUT_BLOCK overrides)
 __global__ void tp_scout_kernel(const float *__restrict__ x, TpPlan g, float *__restrict__ energy)
 {
     // four lanes per reading, 16 bytes each: a wavefront's load covers 16 sectors of 64 bytes (one lane per reading with

@@ -54,7 +54,7 @@ hipError_t launch_demod_fast(const Params &P, const State &S, const Output &O, c
 hipError_t launch_counters(uint32_t *dev, uint32_t *host_mapped, int publish, hipStream_t stream);
 // the log ordered by state column: first [n_bins + 1] (exclusive offsets), sorted [cap] (the records, a column's in any
 // order, their `channel` replaced by their index in the log), cnt [n_bins] scratch; counters[0] = events logged
-uint32_t event_sort_extra_words(uint32_t n_bins);      // words `first` needs behind its n_bins + 1 (the scan's workgroup totals)
+// (`first` needs event_sort_extra_words(n_bins) words behind its n_bins + 1 for the scan's workgroup totals: same_tp_plan.h)
 hipError_t launch_event_sort(const DevEvent *ev, const uint32_t *counters, uint32_t cap, uint32_t n_bins, uint32_t *cnt, uint32_t *first,
                              DevEvent *sorted, hipStream_t stream, bool cnt_is_zero = false);      // cnt_is_zero: the caller emptied cnt on this stream
 // (first_col: columns before it are left alone -- the time-parallel launches copy the channels' own state over them next)
@@ -80,7 +80,6 @@ hipError_t launch_tp_prologue(void *blob, const void *fresh, size_t bytes, uint6
                               uint32_t *counters, hipStream_t stream);
 // Per-channel chunk boundaries for a channel-major input (time-parallel mode): an energy scout over
 // one 64-byte sector per 256-sample block, then per channel the idle instant nearest to every nominal boundary.
-uint32_t tp_scout_block();      // samples per energy reading
 struct TpPlan {
     uint32_t channels, n_chunks, block_len, warmup_samples, whole_samples;
     uint64_t in_samples;      // pitch of a channel in the input
