@@ -397,6 +397,29 @@ uint32_t same_batch_time_parallel_chunks(const same_batch *rx);
  * run on, so it is the faster form of the mode. */
 int same_batch_time_parallel_per_channel(const same_batch *rx);
 
+/* Debug read-back of the plan the device made for the most recent launch (tests/test_tp_planner_gpu.py holds the planning
+ * kernels to a plain reference with it).  Valid after same_batch_sync() following a process call that took the per-channel
+ * path; SAME_EINVAL -- never stale data -- when the last launch had no per-channel plan or is still in flight.  It only
+ * reads: blocking copies from device buffers that nothing is writing.
+ * `info` is always filled.  Each buffer may be null (nothing is copied into it); one that is given must hold at least
+ *   energy    channels * scout_blocks floats: the scout's energy map [channel][reading]
+ *   geom      w_total words: the launch's whole geometry buffer, its arrays at the word offsets w_* (own_start, row0, nominal and
+ *             perm hold n_chunks * channels words each, wg one per 64 grid positions; wg2 -- the workgroups' block counts in
+ *             launch order, then their lengths -- and perm2 are written only when `lpt` is set, and are garbage otherwise)
+ *   handover  n_chunks * channels words: the hand-over instant of every state column (all ones: none)
+ *   final_col channels words: the state column every channel's state was taken from
+ * or the call fails with SAME_EINVAL and copies nothing. */
+typedef struct same_tp_plan_info {
+    uint32_t channels, n_chunks, block_len, warmup_samples, whole_samples, scout_blocks;   /* the planner's arguments */
+    uint32_t sort_mode, lpt, pair_groups;   /* pieces sorted by length; workgroups reordered longest first; ... paired long with short */
+    uint32_t reserved;
+    uint64_t in_samples;                    /* pitch of a channel in the input */
+    uint64_t counter0;                      /* input sample counter of the call's first sample (hand-over instants count from the stream's start) */
+    uint64_t w_own_start, w_row0, w_nominal, w_perm, w_wg, w_wg2, w_perm2, w_total;
+} same_tp_plan_info;
+int same_batch_debug_tp_plan(same_batch *rx, same_tp_plan_info *info, float *energy, size_t energy_cap, uint32_t *geom,
+                             size_t geom_cap, uint64_t *handover, size_t handover_cap, uint32_t *final_col, size_t final_col_cap);
+
 /* 1 when the last process call's transport layer ran on the device (SAME_BATCH_MESSAGES_ONLY, not time-parallel), else 0 */
 int same_batch_transport_on_device(const same_batch *rx);
 

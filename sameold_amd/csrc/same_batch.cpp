@@ -93,6 +93,10 @@ struct same_batch {
         same::TpGeomWords words;             // where each array lies in d_geom, and how much of it comes back
         same::DevBuf<uint32_t> d_geom;
         same::PinnedBuf<uint32_t> h_geom;    // own_start | row0
+        // what the planning kernels were launched with (same_batch_debug_tp_plan reads it back)
+        same::TpPlan plan{};
+        uint64_t plan_counter0 = 0;
+        bool plan_sorted = false, plan_lpt = false, plan_pairs = false;
         // channels re-initialised in front of this launch (same_batch_reset_channels): read in place by the reset kernel
         same::CoherentBuf<uint32_t> h_reset;
         // a ragged call's per-channel counts (same_batch_process_*_ragged): read in place by the ragged kernel
@@ -736,6 +740,8 @@ int tp_plan_boundaries(same_batch *rx, same_batch::Slot &sl, const same::TpCut &
     plan.channels = rx->P.n_channels; plan.n_chunks = cut.n_chunks; plan.block_len = cut.geom.block_len;
     plan.warmup_samples = np.warmup_samples; plan.whole_samples = np.whole_samples; plan.in_samples = np.in_samples;
     plan.scout_blocks = np.scout_blocks;
+    sl.plan = plan; sl.plan_counter0 = rx->counter;
+    sl.plan_sorted = np.sort_mode != 0; sl.plan_lpt = np.lpt; sl.plan_pairs = np.pair_groups;
     uint32_t *g = sl.d_geom;
     // On the library's own stream the planning kernels go to the plan stream: they need the input (ordered by
     // same_batch_order_after, which both streams honour) and this slot's geometry buffers (free since the harvest above),
@@ -1678,6 +1684,40 @@ int same_batch_time_parallel_config(same_batch *rx, uint32_t max_chunks, uint32_
 uint32_t same_batch_time_parallel_chunks(const same_batch *rx) { return rx ? rx->tp.last_chunks : 0; }
 int same_batch_transport_on_device(const same_batch *rx) { return rx && rx->last_dev_transport ? 1 : 0; }
 int same_batch_time_parallel_per_channel(const same_batch *rx) { return rx && rx->tp.last_chunks > 1u && rx->tp.last_per_channel ? 1 : 0; }
+
+int same_batch_debug_tp_plan(same_batch *rx, same_tp_plan_info *info, float *energy, size_t energy_cap, uint32_t *geom,
+                             size_t geom_cap, uint64_t *handover, size_t handover_cap, uint32_t *final_col, size_t final_col_cap)
+{
+    if (!rx || !info) return fail(SAME_EINVAL, "null argument");
+    if (rx->launch_seq == 0) return fail(SAME_EINVAL, "no launch yet");
+    // the most recent launch's slot: its geometry and hand-over buffers are its own; the energy map and the final columns are
+    // the batch's, last written by that launch
+    const same_batch::Slot &sl = rx->slot[(rx->launch_seq - 1) & 1];
+    if (!sl.chunked || !sl.per_channel) return fail(SAME_EINVAL, "the last launch had no per-channel plan");
+    if (rx->slot[0].in_flight || rx->slot[1].in_flight) return fail(SAME_EINVAL, "a launch is in flight: same_batch_sync first");
+    const same::TpPlan &p = sl.plan;
+    const same::TpGeomWords &w = sl.words;
+    const size_t columns = (size_t)p.n_chunks * p.channels, n_energy = (size_t)p.channels * p.scout_blocks;
+    *info = same_tp_plan_info{};
+    info->channels = p.channels; info->n_chunks = p.n_chunks; info->block_len = p.block_len;
+    info->warmup_samples = p.warmup_samples; info->whole_samples = p.whole_samples; info->scout_blocks = p.scout_blocks;
+    info->sort_mode = sl.plan_sorted ? 1u : 0u; info->lpt = sl.plan_lpt ? 1u : 0u; info->pair_groups = sl.plan_pairs ? 1u : 0u;
+    info->in_samples = p.in_samples; info->counter0 = sl.plan_counter0;
+    info->w_own_start = w.own_start; info->w_row0 = w.row0; info->w_nominal = w.nominal; info->w_perm = w.perm;
+    info->w_wg = w.wg; info->w_wg2 = w.wg2; info->w_perm2 = w.perm2; info->w_total = w.total;
+    if ((energy && energy_cap < n_energy) || (geom && geom_cap < w.total) || (handover && handover_cap < columns) ||
+        (final_col && final_col_cap < p.channels))
+        return fail(SAME_EINVAL, "a read-back buffer is too small");
+    if (w.total > sl.d_geom.size() || columns > sl.d_handover.size() || n_energy > rx->tp.d_energy.size() ||
+        p.channels > rx->tp.d_final_col.size())
+        return fail(SAME_EINVAL, "the plan's buffers are gone");
+    HIP_TRY(hipSetDevice(rx->device));
+    if (energy) HIP_TRY(hipMemcpy(energy, rx->tp.d_energy, n_energy * sizeof(float), hipMemcpyDeviceToHost));
+    if (geom) HIP_TRY(hipMemcpy(geom, sl.d_geom, w.total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (handover) HIP_TRY(hipMemcpy(handover, sl.d_handover, columns * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (final_col) HIP_TRY(hipMemcpy(final_col, rx->tp.d_final_col, (size_t)p.channels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SAME_OK;
+}
 
 const char *same_batch_kernel_name(const same_batch *rx)
 {

@@ -648,8 +648,13 @@ __global__ void tp_scout_kernel(const float *__restrict__ x, TpPlan g, float *__
 // blocks before it (the carrier stopped >= 2 048 samples ago: the link layer is back to NoCarrier -- 31 symbols of
 // power history, 1 312 samples, plus the framer's end -- or the chunk simply runs on until it is) to one block after it.
 // "Quiet": below 8 % of the channel's loudest reading.  Among all ways to cut the call at such instants into at most
-// n_chunks pieces the planner takes one that minimises the LONGEST piece (a workgroup runs as long as its longest
-// lane): bisection on that length, each trial a greedy scan that always cuts at the latest allowed instant.  Chunks
+// n_chunks pieces the planner takes one whose LONGEST piece is within one reading of the shortest possible (a workgroup
+// runs as long as its longest lane): a search on that length, each trial a greedy scan that always cuts at the latest
+// allowed instant.  The one reading (min_blocks - 1) is lost where the latest allowed instant in reach, q, lies exactly
+// a limit L behind the previous cut, q + 1 is allowed too and nothing is for a whole limit after it: from q the only
+// instant in reach is q + 1, less than min_blocks away, and the scan gives L up -- although a cut before q, then one at
+// q + 1, fits L where a piece is to spare.  L + 1 cuts at q + 1 and works.  (tests/test_tp_planner_cpu.py pins such a
+// map and holds the plan to an exhaustive optimum: never more than one reading above it.)  Chunks
 // that are left over own nothing (they warm up and hand over at once).  Where a stretch has no quiet instant at all
 // the cut falls where the length limit puts it and the chunk before it runs on until idle, as with uniform boundaries.
 __global__ __launch_bounds__(kWave) void tp_boundaries_kernel(const float *__restrict__ energy, TpPlan g, uint32_t *__restrict__ own_start,

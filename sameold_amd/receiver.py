@@ -98,6 +98,14 @@ class SymbolTrace(C.Structure):
                 ("err", C.c_float), ("samples_until_next_ted", C.c_float)]
 
 
+class TpPlanInfo(C.Structure):
+    """`same_tp_plan_info` (include/same_rx.h)"""
+    _fields_ = [(n, C.c_uint32) for n in ("channels", "n_chunks", "block_len", "warmup_samples", "whole_samples", "scout_blocks",
+                                          "sort_mode", "lpt", "pair_groups", "reserved")] + \
+               [(n, C.c_uint64) for n in ("in_samples", "counter0", "w_own_start", "w_row0", "w_nominal", "w_perm", "w_wg", "w_wg2",
+                                          "w_perm2", "w_total")]
+
+
 _lib = None
 
 
@@ -186,6 +194,7 @@ def load_library() -> C.CDLL:
     sig("same_batch_time_parallel_config", C.c_int, vp, u32, u32, u32)
     sig("same_batch_time_parallel_chunks", u32, vp)
     sig("same_batch_time_parallel_per_channel", C.c_int, vp)
+    sig("same_batch_debug_tp_plan", C.c_int, vp, P(TpPlanInfo), vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t)
     sig("same_batch_transport_on_device", C.c_int, vp)
     sig("same_batch_set_audio_capture", C.c_int, vp, C.c_size_t)
     sig("same_batch_peek_audio", C.c_int, vp, P(P(AudioChunk)), P(C.c_size_t))
@@ -421,6 +430,26 @@ class SameBatchReceiver:
     def time_parallel_per_channel(self) -> bool:
         """Whether that call's chunk boundaries were chosen per channel (channel-major input, see same_rx.h)."""
         return bool(self._L.same_batch_time_parallel_per_channel(self._h))
+
+    def debug_tp_plan(self) -> dict:
+        """The plan the device made for the most recent launch (same_batch_debug_tp_plan): after sync() following a call
+        that took the per-channel path; SameError otherwise.  The scalars of same_tp_plan_info by name, and numpy arrays:
+        `energy` [channels, scout_blocks], `geom` (the whole geometry buffer, its arrays at the word offsets w_*),
+        `handover` [n_chunks, channels] and `final_col` [channels]."""
+        info = TpPlanInfo()
+        none = C.c_void_p()
+        _check(self._L.same_batch_debug_tp_plan(self._h, C.byref(info), none, 0, none, 0, none, 0, none, 0))
+        columns = info.n_chunks * info.channels
+        energy = np.empty((info.channels, info.scout_blocks), np.float32)
+        geom = np.empty(info.w_total, np.uint32)
+        handover = np.empty((info.n_chunks, info.channels), np.uint64)
+        final_col = np.empty(info.channels, np.uint32)
+        _check(self._L.same_batch_debug_tp_plan(self._h, C.byref(info), C.c_void_p(energy.ctypes.data), energy.size,
+                                                C.c_void_p(geom.ctypes.data), geom.size, C.c_void_p(handover.ctypes.data), columns,
+                                                C.c_void_p(final_col.ctypes.data), final_col.size))
+        out = {name: int(getattr(info, name)) for name, _ in TpPlanInfo._fields_ if name != "reserved"}
+        out.update(energy=energy, geom=geom, handover=handover, final_col=final_col)
+        return out
 
     def set_audio_capture(self, samples_per_launch: int) -> None:
         """Capture the alert audio of every message (same_batch_set_audio_capture): messages_only batches that are not
