@@ -1,0 +1,398 @@
+// same_tones.hip -- the tone detector of include/same_tones.h: its kernels and its C ABI.  The arithmetic is
+// same_tones_dev.h's (one text for g++ and the device), positions and the call's work plan same_tones_plan.h's (host only).
+//
+// Blocks are independent of each other: only a channel's open block carries state from call to call.  So the work is
+// parallel over (group of 64 adjacent channels, block of the call): a lane is a channel, a work item runs one block's serial
+// recurrence.  An item loads the saved Acc only when it continues the open block (the call's block 0 of a channel with
+// fill > 0), and saves one only when its block stays open (the call's last block).  Those may be two items running at the
+// same time, so the Acc lives in two banks: a call reads the bank the plan names and saves to the other.  An item whose block
+// completes writes P_0..2 and Em (when asked) and the block's two qualify bits.
+//   tones_tm_kernel  time-major: lane c reads x[r * C + c].  Lanes whose block phases agree read one row together.
+//   tones_cm_kernel  channel-major: a wavefront stages tiles of 64 channels x 64 samples through LDS -- loaded with the lanes
+//                    along time (256 or 128 contiguous bytes of one channel), consumed with the lanes along channels from rows
+//                    padded to 65 words, so that the 32 lanes of a half read 32 different banks.  A tile's 64 loads are
+//                    issued together into registers, one tile ahead of the arithmetic.  One wavefront per
+//                    workgroup: the two barriers around a tile are that wavefront's own, and the trip counts they sit in
+//                    are the same in every lane (the longest block of the 64 channels, by a butterfly of shuffles).
+//   tones_sm_kernel  lane = channel: both state machines over the call's qualify bits, events into the channel's own slots.
+// No atomics, no word passed between wavefronts.  Behind the kernels one copy of the call's counts and event slots into the
+// pinned buffer of one of kSlots slots, and an event record; a slot is reused only once its event has passed and its events
+// have been taken into the host queue.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/same_tones.h"
+#include "same_hipmem.h"
+#include "same_tones_plan.h"
+
+namespace same {
+namespace {
+
+constexpr uint32_t kItemsPerBlock = 4;            // time-major: wavefronts of a workgroup, each on a block of its own
+constexpr uint32_t kMaxGridY = 65535;
+constexpr uint32_t kTile = 64, kTilePitch = kTile + 1;
+constexpr int kSlots = 3;
+constexpr uint64_t kMaxCallBytes = 1ull << 31;    // counts and event slots of one call
+
+template <typename SampleT>
+__global__ __launch_bounds__(64 * kItemsPerBlock) void tones_tm_kernel(const tn::Desc *__restrict__ desc, tn::Coef cf, const SampleT *__restrict__ x,
+                                                                       float *__restrict__ acc, float *__restrict__ blocks,
+                                                                       uint8_t *__restrict__ qual, uint32_t n_channels, uint32_t n_items)
+{
+    const uint32_t c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= n_channels) return;
+    const tn::Desc d = desc[c];
+    const size_t bank_words = (size_t)tn::kAccWords * n_channels;
+    const float *bank_in = acc + ((d.flags & tn::kDescBank) ? bank_words : 0);
+    float *bank_out = acc + ((d.flags & tn::kDescBank) ? 0 : bank_words);
+    for (uint32_t j = blockIdx.y * kItemsPerBlock + threadIdx.y; j < n_items; j += gridDim.y * kItemsPerBlock) {
+        if (j >= d.n_touch) return;               // this and every later block lies behind the channel's samples
+        uint32_t r0, r1;
+        tn::block_rows(d, cf.N, j, r0, r1);
+        tn::Acc a = tn::block_continues(d, j) ? tn::acc_load(bank_in, n_channels, c) : tn::acc_zero();
+        tn::run_rows(a, cf, x + c, n_channels, r0, r1);
+        tn::block_end(d, cf, j, a, c, n_channels, blocks, qual, bank_out);
+    }
+}
+
+// One tile of the channel-major kernel into registers: v[ch] = the sample of channel c0 + ch at row r0(ch) + k0 + lane of the
+// call, where r0(ch), r1(ch) are lane ch's block bounds.  A lane whose row lies at or beyond r1(ch) -- the block is shorter, or
+// there is no such channel (r1 == 0) -- loads x[star_at + k0] instead, a sample the group's longest block owns, and nobody
+// consumes what it loaded: rows at or beyond a channel's count are never loaded, and no load hangs on a branch.
+template <typename SampleT>
+__device__ __forceinline__ void cm_load_tile(SampleT (&v)[kTile], const SampleT *__restrict__ x, size_t n_rows, uint32_t c0, uint32_t lane,
+                                             uint32_t r0, uint32_t r1, uint32_t k0, size_t star_at)
+{
+#pragma unroll
+    for (uint32_t ch = 0; ch < kTile; ++ch) {
+        const uint32_t cr0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, (int)ch), cr1 = (uint32_t)__builtin_amdgcn_readlane((int)r1, (int)ch);
+        const uint64_t t = (uint64_t)cr0 + k0 + lane;
+        const size_t at = t < cr1 ? (size_t)(c0 + ch) * n_rows + (size_t)t : star_at + k0;
+        v[ch] = x[at];
+    }
+}
+
+template <typename SampleT>
+__global__ __launch_bounds__(64) void tones_cm_kernel(const tn::Desc *__restrict__ desc, tn::Coef cf, const SampleT *__restrict__ x, size_t n_rows,
+                                                      float *__restrict__ acc, float *__restrict__ blocks, uint8_t *__restrict__ qual,
+                                                      uint32_t n_channels, uint32_t n_items)
+{
+    __shared__ float tile[kTile * kTilePitch];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t c0 = blockIdx.x * kTile, c = c0 + lane;
+    const bool valid = c < n_channels;
+    tn::Desc d{};                                  // (n_touch == 0: a lane without a channel owns no block)
+    if (valid) d = desc[c];
+    const size_t bank_words = (size_t)tn::kAccWords * n_channels;
+    const float *bank_in = acc + ((d.flags & tn::kDescBank) ? bank_words : 0);
+    float *bank_out = acc + ((d.flags & tn::kDescBank) ? 0 : bank_words);
+    for (uint32_t j = blockIdx.y; j < n_items; j += gridDim.y) {
+        const bool mine = j < d.n_touch;
+        uint32_t r0 = 0, r1 = 0;
+        if (mine) tn::block_rows(d, cf.N, j, r0, r1);
+        const uint32_t len = r1 - r0;              // (> 0 for a block the channel touches)
+        uint32_t longest = len;
+        for (int m = 32; m > 0; m >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)longest, m, 64);
+            longest = o > longest ? o : longest;
+        }
+        if (longest == 0) break;                   // the same in every lane: no channel of the group reaches block j or a later one
+        // the first lane whose block is the longest: row r0 + k of its channel is one the channel owns for every k < longest,
+        // the address a lane loads from when its own position lies outside the block it loads for
+        const uint32_t star = (uint32_t)__builtin_ctzll(__ballot(len == longest));
+        const size_t star_at = (size_t)(c0 + star) * n_rows + (uint32_t)__builtin_amdgcn_readlane((int)r0, (int)star);
+        tn::Acc a = mine && tn::block_continues(d, j) ? tn::acc_load(bank_in, n_channels, c) : tn::acc_zero();
+        // A tile's 64 loads are issued together, unconditionally, into registers, one tile ahead of the arithmetic: while
+        // the lanes consume tile k from LDS the loads of tile k + 1 are in flight.
+        SampleT v[kTile];
+        cm_load_tile(v, x, n_rows, c0, lane, r0, r1, 0, star_at);
+        for (uint32_t k0 = 0; k0 < longest; k0 += kTile) {
+            __syncthreads();                       // (the tile before this one has been consumed)
+#pragma unroll
+            for (uint32_t ch = 0; ch < kTile; ++ch) tile[ch * kTilePitch + lane] = (float)v[ch];
+            __syncthreads();
+            if (k0 + kTile < longest) cm_load_tile(v, x, n_rows, c0, lane, r0, r1, k0 + kTile, star_at);
+            const uint32_t left = len > k0 ? len - k0 : 0, n = left < kTile ? left : kTile;
+            for (uint32_t i = 0; i < n; ++i) tn::step(a, cf, tile[lane * kTilePitch + i]);
+        }
+        if (mine) tn::block_end(d, cf, j, a, c, n_channels, blocks, qual, bank_out);
+    }
+}
+
+__global__ __launch_bounds__(256) void tones_sm_kernel(const tn::Desc *__restrict__ desc, uint32_t N, const uint8_t *__restrict__ qual,
+                                                       tn::Sm *__restrict__ sm, uint32_t *__restrict__ ev_counts,
+                                                       same_tone_event *__restrict__ ev, uint32_t n_channels)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_channels) return;
+    const tn::Desc d = desc[c];
+    tn::Sm s[2] = {sm[2 * (size_t)c], sm[2 * (size_t)c + 1]};
+    ev_counts[c] = tn::run_state_machines(d, N, c, n_channels, qual, s, ev);
+    sm[2 * (size_t)c] = s[0];
+    sm[2 * (size_t)c + 1] = s[1];
+}
+
+thread_local std::string g_tones_error;
+
+int fail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_tones_error = buf;
+    return code;
+}
+
+#define TN_HIP_TRY(expr)                                                                                            \
+    do {                                                                                                            \
+        hipError_t _e = (expr);                                                                                     \
+        if (_e != hipSuccess) return fail(SAME_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+    } while (0)
+
+// a call's counts and event slots, on the device and in a slot: n_channels counts, padded to 32 bytes, then the events
+size_t events_offset(uint32_t n_channels) { return (((size_t)n_channels * sizeof(uint32_t)) + 31) / 32 * 32; }
+
+}  // namespace
+}  // namespace same
+
+struct same_tones {
+    same::TonesPlan plan;
+    int device = 0;
+    same::DevBuf<same::tn::Desc> d_desc;         // the descriptors of the call the stream is at
+    same::DevBuf<float> d_acc;                   // two banks of [tn::kAccWords x C]: the channels' open blocks
+    same::DevBuf<same::tn::Sm> d_sm;             // [C x 2]: attention, wat
+    same::DevBuf<uint8_t> d_qual;                // [blocks completed x C]: the qualify bits of the call the stream is at
+    same::DevBuf<uint8_t> d_out;                 // its counts and event slots
+    struct Slot {
+        same::PinnedBuf<same::tn::Desc> desc;
+        same::PinnedBuf<uint8_t> out;
+        same::Event done;
+        bool in_flight = false;
+    };
+    Slot slot[same::kSlots];
+    int next_slot = 0;                           // (the slots are used in turn: the oldest call in flight is in next_slot)
+    std::vector<same_tone_event> queue;          // events of the calls that have passed, from queue_head on
+    size_t queue_head = 0;
+};
+
+namespace same {
+namespace {
+
+// the events of a call that has passed, by channel and inside a channel in the order its lane wrote them
+void harvest(same_tones *h, same_tones::Slot &s)
+{
+    const uint32_t C = h->plan.n_channels();
+    if (h->queue_head == h->queue.size()) { h->queue.clear(); h->queue_head = 0; }
+    const uint32_t *counts = (const uint32_t *)s.out.get();
+    const uint8_t *events = s.out.get() + events_offset(C);
+    for (uint32_t c = 0; c < C; ++c)
+        for (uint32_t i = 0; i < counts[c]; ++i) {
+            same_tone_event e;
+            std::memcpy(&e, events + ((size_t)s.desc[c].ev_off + i) * sizeof(same_tone_event), sizeof(e));
+            h->queue.push_back(e);
+        }
+    s.in_flight = false;
+}
+
+int wait_slot(same_tones *h, same_tones::Slot &s)
+{
+    if (!s.in_flight) return SAME_OK;
+    TN_HIP_TRY(hipEventSynchronize(s.done));
+    harvest(h, s);
+    return SAME_OK;
+}
+
+// the slots whose calls have passed, oldest first, up to the first that has not
+int collect(same_tones *h, bool wait)
+{
+    for (int i = 0; i < kSlots; ++i) {
+        same_tones::Slot &s = h->slot[(h->next_slot + i) % kSlots];
+        if (!s.in_flight) continue;
+        if (wait) { const int rc = wait_slot(h, s); if (rc) return rc; continue; }
+        const hipError_t e = hipEventQuery(s.done);
+        if (e == hipErrorNotReady) break;
+        if (e != hipSuccess) return fail(SAME_EHIP, "hipEventQuery failed: %s", hipGetErrorString(e));
+        harvest(h, s);
+    }
+    return SAME_OK;
+}
+
+template <typename SampleT>
+int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *counts, int layout, float *d_blocks, size_t block_rows,
+            void *hip_stream)
+{
+    if (!h) return fail(SAME_EINVAL, "null handle");
+    if (layout != SAME_LAYOUT_TIME_MAJOR && layout != SAME_LAYOUT_CHANNEL_MAJOR)
+        return fail(SAME_EINVAL, "layout %d is neither time-major nor channel-major; nothing was consumed", layout);
+    const uint32_t C = h->plan.n_channels();
+    uint32_t max_blocks = 0;
+    if (h->plan.block_counts(counts, n_rows, nullptr, &max_blocks))
+        return fail(SAME_EINVAL, "a count exceeds n_rows = %zu, or n_rows exceeds 2^32 - 1; nothing was consumed", n_rows);
+    if (d_blocks && max_blocks > block_rows)
+        return fail(SAME_EINVAL, "block_rows = %zu, the call completes up to %u blocks; nothing was consumed", block_rows, max_blocks);
+    TN_HIP_TRY(hipSetDevice(h->device));
+    same_tones::Slot &s = h->slot[h->next_slot];
+    int rc = wait_slot(h, s);
+    if (rc) return rc;
+    const TonesPlan::Shape shape = h->plan.describe(counts, n_rows, s.desc.get());
+    if (!shape.any_samples) return SAME_OK;       // nothing to read: a no-op (a pending reset stays pending)
+    if (!d_x) return fail(SAME_EINVAL, "null d_x with samples to read; nothing was consumed");
+    const uint64_t out_bytes = events_offset(C) + shape.event_slots * sizeof(same_tone_event);
+    if (out_bytes > kMaxCallBytes) return fail(SAME_ENOMEM, "the call needs %llu bytes of event slots; nothing was consumed", (unsigned long long)out_bytes);
+    // (a buffer that grows is freed first, which waits for the device: nothing in flight loses it)
+    hipError_t e = h->d_qual.ensure((size_t)(shape.max_complete ? shape.max_complete : 1) * C);
+    if (e == hipSuccess) e = h->d_out.ensure((size_t)out_bytes);
+    if (e == hipSuccess) e = s.out.ensure((size_t)out_bytes);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the call's buffers failed: %s; nothing was consumed", hipGetErrorString(e));
+
+    hipStream_t stream = (hipStream_t)hip_stream;
+    TN_HIP_TRY(hipMemcpyAsync(h->d_desc.get(), s.desc.get(), (size_t)C * sizeof(tn::Desc), hipMemcpyHostToDevice, stream));
+    const uint32_t groups = (C + 63) / 64;
+    if (layout == SAME_LAYOUT_TIME_MAJOR) {
+        const uint32_t gy = (shape.max_touch + kItemsPerBlock - 1) / kItemsPerBlock;
+        hipLaunchKernelGGL(tones_tm_kernel<SampleT>, dim3(groups, gy < kMaxGridY ? gy : kMaxGridY), dim3(64, kItemsPerBlock), 0, stream,
+                           h->d_desc.get(), h->plan.coef, d_x, h->d_acc.get(), d_blocks, h->d_qual.get(), C, shape.max_touch);
+    } else {
+        hipLaunchKernelGGL(tones_cm_kernel<SampleT>, dim3(groups, shape.max_touch < kMaxGridY ? shape.max_touch : kMaxGridY), dim3(64), 0,
+                           stream, h->d_desc.get(), h->plan.coef, d_x, n_rows, h->d_acc.get(), d_blocks, h->d_qual.get(), C, shape.max_touch);
+    }
+    TN_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tones_sm_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, h->d_desc.get(), h->plan.coef.N, h->d_qual.get(),
+                       h->d_sm.get(), (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)), C);
+    TN_HIP_TRY(hipGetLastError());
+    TN_HIP_TRY(hipMemcpyAsync(s.out.get(), h->d_out.get(), (size_t)out_bytes, hipMemcpyDeviceToHost, stream));
+    TN_HIP_TRY(hipEventRecord(s.done, stream));
+    s.in_flight = true;
+    h->next_slot = (h->next_slot + 1) % kSlots;
+    h->plan.commit(s.desc.get());
+    return SAME_OK;
+}
+
+}  // namespace
+}  // namespace same
+
+using namespace same;
+
+extern "C" {
+
+const char *same_tones_last_error(void) { return g_tones_error.c_str(); }
+
+int same_tones_new(uint32_t n_channels, uint32_t rate, int device, same_tones **out)
+{
+    if (!out) return fail(SAME_EINVAL, "null out");
+    *out = nullptr;
+    same_tones *h = new (std::nothrow) same_tones;
+    if (!h) return fail(SAME_ENOMEM, "out of memory");
+    // (the plan first: a refused rate is refused with or without a device)
+    const int rc = h->plan.init(n_channels, rate);
+    if (rc) {
+        delete h;
+        return rc == SAME_ERATE ? fail(rc, "rate %u Hz is outside %u .. %u Hz", rate, SAME_TONES_MIN_RATE, SAME_TONES_MAX_RATE)
+                                : fail(rc, "zero channels");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete h; return fail(SAME_ENODEVICE, "no HIP device visible (this library has no CPU path)"); }
+    if (device < 0 || device >= ndev) { delete h; return fail(SAME_ENODEVICE, "device %d out of range (%d visible)", device, ndev); }
+    h->device = device;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = h->d_desc.ensure(n_channels);
+    if (e == hipSuccess) e = h->d_acc.ensure((size_t)2 * tn::kAccWords * n_channels);      // (read only where a call saved before)
+    if (e == hipSuccess) e = h->d_sm.ensure((size_t)2 * n_channels);                        // (made idle by the first call that runs)
+    for (same_tones::Slot &s : h->slot) {
+        if (e == hipSuccess) e = s.desc.ensure(n_channels);
+        if (e == hipSuccess) e = s.done.ensure();
+    }
+    if (e != hipSuccess) {
+        delete h;
+        return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the tone detector failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return SAME_OK;
+}
+
+void same_tones_free(same_tones *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    // (the kernels in flight read the handle's buffers)
+    for (same_tones::Slot &s : h->slot)
+        if (s.in_flight) (void)hipEventSynchronize(s.done);
+    delete h;
+}
+
+uint32_t same_tones_n_channels(const same_tones *h) { return h ? h->plan.n_channels() : 0; }
+uint32_t same_tones_rate(const same_tones *h) { return h ? h->plan.rate : 0; }
+uint32_t same_tones_block_length(const same_tones *h) { return h ? h->plan.coef.N : 0; }
+
+int same_tones_coefficients(const same_tones *h, float out[3])
+{
+    if (!h || !out) return fail(SAME_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out[k] = h->plan.coef.c[k];
+    return SAME_OK;
+}
+
+int same_tones_block_counts(const same_tones *h, const uint32_t *counts, size_t n_rows, uint32_t *block_counts, uint32_t *max_blocks)
+{
+    if (!h || !block_counts || !max_blocks) return fail(SAME_EINVAL, "null argument");
+    if (h->plan.block_counts(counts, n_rows, block_counts, max_blocks))
+        return fail(SAME_EINVAL, "a count exceeds n_rows = %zu, or n_rows exceeds 2^32 - 1", n_rows);
+    return SAME_OK;
+}
+
+int same_tones_process_device(same_tones *h, const float *d_x, size_t n_rows, const uint32_t *counts, int layout, float *d_blocks,
+                              size_t block_rows, void *hip_stream)
+{
+    return process(h, d_x, n_rows, counts, layout, d_blocks, block_rows, hip_stream);
+}
+
+int same_tones_process_device_i16(same_tones *h, const int16_t *d_x, size_t n_rows, const uint32_t *counts, int layout, float *d_blocks,
+                                  size_t block_rows, void *hip_stream)
+{
+    return process(h, d_x, n_rows, counts, layout, d_blocks, block_rows, hip_stream);
+}
+
+int same_tones_sync(same_tones *h)
+{
+    if (!h) return fail(SAME_EINVAL, "null handle");
+    TN_HIP_TRY(hipSetDevice(h->device));
+    return collect(h, true);
+}
+
+int same_tones_poll(same_tones *h, same_tone_event *out, size_t cap, size_t *n_out, size_t *n_left)
+{
+    if (!h || (!out && cap) || !n_out) return fail(SAME_EINVAL, "null argument");
+    *n_out = 0;
+    TN_HIP_TRY(hipSetDevice(h->device));
+    const int rc = collect(h, false);
+    if (rc) return rc;
+    size_t have = h->queue.size() - h->queue_head;
+    const size_t n = have < cap ? have : cap;
+    if (n) std::memcpy(out, h->queue.data() + h->queue_head, n * sizeof(same_tone_event));
+    h->queue_head += n;
+    *n_out = n;
+    if (n_left) *n_left = have - n;
+    return SAME_OK;
+}
+
+int same_tones_reset_channels(same_tones *h, const uint32_t *channels, size_t n)
+{
+    if (!h || (!channels && n)) return fail(SAME_EINVAL, "null argument");
+    if (h->plan.reset(channels, n)) return fail(SAME_EINVAL, "a channel out of range; nothing was reset");
+    return SAME_OK;
+}
+
+uint64_t same_tones_channel_sample_counter(const same_tones *h, uint32_t channel)
+{
+    return h && channel < h->plan.n_channels() ? h->plan.pos[channel] : 0;
+}
+
+}  // extern "C"
