@@ -18,17 +18,25 @@
 // No atomics, no word passed between wavefronts.  Behind the kernels one copy of the call's counts and event slots into the
 // pinned buffer of one of kSlots slots, and an event record; a slot is reused only once its event has passed and its events
 // have been taken into the host queue.
+// Tone-alert audio (include/same_tone_audio.h): a handle whose capture is on queues, in place of
+// tones_sm_kernel, the capture-aware state-machine kernel, the prefix kernel and the layout's copy kernel of same_tone_audio.hip,
+// and copies the call's chunk records behind its event slots.  The samples stay in the slot's pool on the device until the
+// call has passed and someone asks for them (fetch_block): same_tone_audio_peek, or the call that takes the slot next.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "../../include/same_tone_audio.h"
 #include "../../include/same_tones.h"
 #include "same_hipmem.h"
+#include "same_tone_audio_kernels.h"
+#include "same_tone_audio_plan.h"
 #include "same_tones_plan.h"
 
 namespace same {
@@ -163,10 +171,19 @@ size_t events_offset(uint32_t n_channels) { return (((size_t)n_channels * sizeof
 }  // namespace
 }  // namespace same
 
+// the samples of one call, on the host once fetched
+struct AudioBlock {
+    std::vector<float> data;
+    size_t chunks = 0;                           // queued chunks of the call that have not been dropped
+    uint64_t used = 0;                           // samples of the call's pool in use
+    int slot = -1;                               // the slot whose pool holds them until they are fetched; -1: fetched
+    bool published = false;                     // its chunks are in the peek view
+};
+
 struct same_tones {
     same::TonesPlan plan;
     int device = 0;
-    same::DevBuf<same::tn::Desc> d_desc;         // the descriptors of the call the stream is at
+    same::DevBuf<same::tn::Desc> d_desc;         // the descriptors of the call the stream is at; behind them its chunk-slot offsets
     same::DevBuf<float> d_acc;                   // two banks of [tn::kAccWords x C]: the channels' open blocks
     same::DevBuf<same::tn::Sm> d_sm;             // [C x 2]: attention, wat
     same::DevBuf<uint8_t> d_qual;                // [blocks completed x C]: the qualify bits of the call the stream is at
@@ -176,11 +193,29 @@ struct same_tones {
         same::PinnedBuf<uint8_t> out;
         same::Event done;
         bool in_flight = false;
+        // tone-alert audio: the call's chunk records, its sample pool, and the host block that still waits for the pool's samples
+        same::PinnedBuf<uint8_t> cap_out;
+        same::DevBuf<float> pool;
+        bool captures = false;                   // the call in this slot ran with capture on
+        AudioBlock *unfetched = nullptr;
     };
     Slot slot[same::kSlots];
     int next_slot = 0;                           // (the slots are used in turn: the oldest call in flight is in next_slot)
     std::vector<same_tone_event> queue;          // events of the calls that have passed, from queue_head on
     size_t queue_head = 0;
+    bool fed = false;                            // a call has consumed samples
+
+    // tone-alert audio
+    same::ToneAudioPlan audio;
+    same::DevBuf<same::tn::Cap> d_cap;           // [C]
+    same::DevBuf<uint64_t> d_cap_counts;         // [C]: captured rows of the call the stream is at
+    same::DevBuf<uint32_t> d_cap_flags;          // [ceil(C / 64)]
+    same::DevBuf<uint8_t> d_cap_out;             // its chunk records
+    hipStream_t copy_stream = nullptr;           // the lazy copies of the pools' used parts
+    std::deque<AudioBlock> blocks;               // the samples of the calls whose chunks are queued, oldest first
+    std::vector<same_tone_audio_chunk> pending;  // chunks of harvested calls (samples: the offset in the call's pool) ...
+    std::vector<same_tone_audio_chunk> ready;    // ... and, from ready_head on, the view same_tone_audio_peek hands out
+    size_t ready_head = 0;
 };
 
 namespace same {
@@ -200,6 +235,39 @@ void harvest(same_tones *h, same_tones::Slot &s)
             h->queue.push_back(e);
         }
     s.in_flight = false;
+    if (!s.captures) return;
+    // its chunks, by channel and inside a channel in stream order; their samples stay in the slot's pool for now
+    const uint64_t *header = (const uint64_t *)s.cap_out.get();
+    const uint32_t *n_spans = (const uint32_t *)(s.cap_out.get() + kCapHeaderBytes);
+    const uint8_t *spans = s.cap_out.get() + cap_spans_offset(C);
+    const uint32_t *span_off = (const uint32_t *)(s.desc.get() + C);
+    size_t n = 0;
+    for (uint32_t c = 0; c < C; ++c)
+        for (uint32_t i = 0; i < n_spans[c]; ++i, ++n) {
+            tn::Span sp;
+            std::memcpy(&sp, spans + ((size_t)span_off[c] + i) * sizeof(tn::Span), sizeof(sp));
+            h->pending.push_back(same_tone_audio_chunk{sp.channel, sp.flags, sp.kind, 0, sp.sample_counter, sp.n, sp.tone_start,
+                                                       (const float *)(uintptr_t)(sp.off * sizeof(float))});
+        }
+    if (!n) return;
+    h->blocks.emplace_back();
+    AudioBlock &b = h->blocks.back();
+    b.chunks = n;
+    b.used = header[1];
+    if (b.used) { b.slot = (int)(&s - h->slot); s.unfetched = &b; }
+}
+
+// the used part of a passed call's pool into its host block: waits for that copy, never for a call in flight
+int fetch_block(same_tones *h, AudioBlock &b)
+{
+    if (b.slot < 0) return SAME_OK;
+    same_tones::Slot &s = h->slot[b.slot];
+    try { b.data.resize((size_t)b.used); } catch (...) { return fail(SAME_ENOMEM, "%llu captured samples on the host", (unsigned long long)b.used); }
+    TN_HIP_TRY(hipMemcpyAsync(b.data.data(), s.pool.get(), (size_t)b.used * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
+    TN_HIP_TRY(hipStreamSynchronize(h->copy_stream));
+    b.slot = -1;
+    s.unfetched = nullptr;
+    return SAME_OK;
 }
 
 int wait_slot(same_tones *h, same_tones::Slot &s)
@@ -253,9 +321,21 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
     if (e == hipSuccess) e = s.out.ensure((size_t)out_bytes);
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the call's buffers failed: %s; nothing was consumed", hipGetErrorString(e));
+    // capture on: the chunk slots behind the descriptors, room for the chunk records, and the slot's pool free to be written
+    const bool capture = h->audio.on();
+    uint64_t cap_bytes = 0;
+    if (capture) {
+        if (s.unfetched && (rc = fetch_block(h, *s.unfetched))) return rc;
+        cap_bytes = cap_spans_offset(C) + ToneAudioPlan::describe(s.desc.get(), C, (uint32_t *)(s.desc.get() + C)) * sizeof(tn::Span);
+        if (cap_bytes > kMaxCallBytes) return fail(SAME_ENOMEM, "the call needs %llu bytes of chunk slots; nothing was consumed", (unsigned long long)cap_bytes);
+        e = h->d_cap_out.ensure((size_t)cap_bytes);
+        if (e == hipSuccess) e = s.cap_out.ensure((size_t)cap_bytes);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the call's chunk records failed: %s; nothing was consumed", hipGetErrorString(e));
+    }
 
     hipStream_t stream = (hipStream_t)hip_stream;
-    TN_HIP_TRY(hipMemcpyAsync(h->d_desc.get(), s.desc.get(), (size_t)C * sizeof(tn::Desc), hipMemcpyHostToDevice, stream));
+    TN_HIP_TRY(hipMemcpyAsync(h->d_desc.get(), s.desc.get(), (size_t)C * (sizeof(tn::Desc) + (capture ? sizeof(uint32_t) : 0)), hipMemcpyHostToDevice, stream));
     const uint32_t groups = (C + 63) / 64;
     if (layout == SAME_LAYOUT_TIME_MAJOR) {
         const uint32_t gy = (shape.max_touch + kItemsPerBlock - 1) / kItemsPerBlock;
@@ -266,12 +346,24 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
                            stream, h->d_desc.get(), h->plan.coef, d_x, n_rows, h->d_acc.get(), d_blocks, h->d_qual.get(), C, shape.max_touch);
     }
     TN_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tones_sm_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, h->d_desc.get(), h->plan.coef.N, h->d_qual.get(),
-                       h->d_sm.get(), (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)), C);
-    TN_HIP_TRY(hipGetLastError());
+    if (capture) {
+        const ToneAudioCall k{h->d_desc.get(), (const uint32_t *)(h->d_desc.get() + C), h->d_qual.get(), h->d_sm.get(), h->d_cap.get(),
+                              h->audio.params, (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)),
+                              h->d_cap_out.get(), h->d_cap_counts.get(), h->d_cap_flags.get(), s.pool.get(), h->audio.pool_cap,
+                              h->plan.coef.N, C};
+        TN_HIP_TRY(tone_audio_launch_sm(k, stream));
+        TN_HIP_TRY(tone_audio_launch_copy(k, d_x, n_rows, layout, stream));
+        TN_HIP_TRY(hipMemcpyAsync(s.cap_out.get(), h->d_cap_out.get(), (size_t)cap_bytes, hipMemcpyDeviceToHost, stream));
+    } else {
+        hipLaunchKernelGGL(tones_sm_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, h->d_desc.get(), h->plan.coef.N, h->d_qual.get(),
+                           h->d_sm.get(), (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)), C);
+        TN_HIP_TRY(hipGetLastError());
+    }
     TN_HIP_TRY(hipMemcpyAsync(s.out.get(), h->d_out.get(), (size_t)out_bytes, hipMemcpyDeviceToHost, stream));
     TN_HIP_TRY(hipEventRecord(s.done, stream));
     s.in_flight = true;
+    s.captures = capture;
+    h->fed = true;
     h->next_slot = (h->next_slot + 1) % kSlots;
     h->plan.commit(s.desc.get());
     return SAME_OK;
@@ -326,8 +418,93 @@ void same_tones_free(same_tones *h)
     // (the kernels in flight read the handle's buffers)
     for (same_tones::Slot &s : h->slot)
         if (s.in_flight) (void)hipEventSynchronize(s.done);
+    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     delete h;
 }
+
+int same_tone_audio_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, uint32_t max_blocks, size_t samples_per_call)
+{
+    if (!h) return fail(SAME_EINVAL, "null handle");
+    if (h->fed) return fail(SAME_EINVAL, "capture is set before the handle's first sample");
+    ToneAudioPlan plan;
+    if (plan.set(kinds, tail_blocks, max_blocks, samples_per_call))
+        return fail(SAME_EINVAL, "kinds = %u is not a non-zero mask of SAME_TONE_ATTENTION | SAME_TONE_WAT, or max_blocks = %u is zero", kinds, max_blocks);
+    TN_HIP_TRY(hipSetDevice(h->device));
+    h->audio = ToneAudioPlan();                   // (off until everything is there)
+    hipError_t e = hipSuccess;
+    if (!plan.on()) {
+        for (same_tones::Slot &s : h->slot)
+            if (e == hipSuccess) e = s.pool.reset();
+        if (e != hipSuccess) return fail(SAME_EHIP, "freeing the pools failed: %s", hipGetErrorString(e));
+        return SAME_OK;
+    }
+    const uint32_t C = h->plan.n_channels();
+    const size_t desc_room = (size_t)C + ((size_t)C * sizeof(uint32_t) + sizeof(tn::Desc) - 1) / sizeof(tn::Desc);   // descriptors, then C chunk-slot offsets
+    if (!h->copy_stream) e = hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = h->d_desc.ensure(desc_room);
+    if (e == hipSuccess) e = h->d_cap.ensure(C);                                  // (made zero by the first call that runs)
+    if (e == hipSuccess) e = h->d_cap_counts.ensure(C);
+    if (e == hipSuccess) e = h->d_cap_flags.ensure((C + 63) / 64);
+    for (same_tones::Slot &s : h->slot) {
+        if (e == hipSuccess) e = s.desc.ensure(desc_room);
+        if (e == hipSuccess) e = s.pool.reset();
+        if (e == hipSuccess) e = s.pool.ensure(samples_per_call);
+    }
+    if (e != hipSuccess) {
+        for (same_tones::Slot &s : h->slot) (void)s.pool.reset();
+        return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the capture's pools (3 x %zu samples) failed: %s; capture is off", samples_per_call,
+                    hipGetErrorString(e));
+    }
+    h->audio = plan;
+    return SAME_OK;
+}
+
+int same_tone_audio_peek(same_tones *h, const same_tone_audio_chunk **chunks, size_t *n)
+{
+    if (!h || !chunks || !n) return fail(SAME_EINVAL, "null argument");
+    *chunks = nullptr;
+    *n = 0;
+    TN_HIP_TRY(hipSetDevice(h->device));
+    int rc = collect(h, false);
+    if (rc) return rc;
+    if (h->ready_head == h->ready.size()) { h->ready.clear(); h->ready_head = 0; }
+    // the harvested calls' samples come to the host, and their chunks into the view
+    size_t at = 0;
+    for (AudioBlock &b : h->blocks) {
+        if (b.published) continue;
+        if ((rc = fetch_block(h, b))) break;
+        try { h->ready.reserve(h->ready.size() + b.chunks); } catch (...) { rc = fail(SAME_ENOMEM, "audio view"); break; }
+        for (size_t i = 0; i < b.chunks; ++i) {
+            same_tone_audio_chunk ch = h->pending[at + i];
+            ch.samples = ch.n_samples ? b.data.data() + (uintptr_t)ch.samples / sizeof(float) : nullptr;
+            h->ready.push_back(ch);
+        }
+        at += b.chunks;
+        b.published = true;
+    }
+    h->pending.erase(h->pending.begin(), h->pending.begin() + (ptrdiff_t)at);
+    if (rc) return rc;
+    *n = h->ready.size() - h->ready_head;
+    *chunks = *n ? h->ready.data() + h->ready_head : nullptr;
+    return SAME_OK;
+}
+
+int same_tone_audio_drop(same_tones *h, size_t n)
+{
+    if (!h) return fail(SAME_EINVAL, "null argument");
+    if (n > h->ready.size() - h->ready_head) return fail(SAME_EINVAL, "more chunks than the view holds");
+    h->ready_head += n;
+    while (n) {                                   // (the view's chunks are those of the oldest blocks)
+        AudioBlock &b = h->blocks.front();
+        const size_t k = n < b.chunks ? n : b.chunks;
+        b.chunks -= k;
+        n -= k;
+        if (b.chunks == 0) h->blocks.pop_front();
+    }
+    return SAME_OK;
+}
+
+uint32_t same_tone_audio_chunk_bound(uint32_t n_blocks) { return tn::chunk_bound(n_blocks); }
 
 uint32_t same_tones_n_channels(const same_tones *h) { return h ? h->plan.n_channels() : 0; }
 uint32_t same_tones_rate(const same_tones *h) { return h ? h->plan.rate : 0; }

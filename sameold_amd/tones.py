@@ -7,6 +7,10 @@ a batch reads and reports tone events that count in each channel's own samples.
     td.process(x, counts)           # or a ragged call: channel c owns its first counts[c] rows
     td.sync(); events = td.poll()   # numpy records: channel, kind, edge, reserved, sample_counter, duration
 
+Tone alert (include/same_tone_audio.h): `td.set_audio_capture(TONE_WAT | TONE_ATTENTION, tail_blocks, max_blocks,
+samples_per_call)` before the first sample makes the same `process` calls copy what follows a confirmed tone out of `x` on the
+device; `td.sync(); td.poll_audio()` hands the chunks out.
+
 There is no CPU fallback: the detection runs in the library's gfx950 kernels or not at all.
 """
 from __future__ import annotations
@@ -30,6 +34,18 @@ TONE_MIN_RATE, TONE_MAX_RATE = 8000, 96000
 TONE_EVENT_DTYPE = np.dtype([("channel", "<u4"), ("kind", "<u4"), ("edge", "<u4"), ("reserved", "<u4"),
                              ("sample_counter", "<u8"), ("duration", "<u8")])
 assert TONE_EVENT_DTYPE.itemsize == 32
+
+# tone-alert audio (include/same_tone_audio.h): same_tone_audio_chunk.flags, and the record as the library lays it out
+TONE_AUDIO_FIRST, TONE_AUDIO_END_TAIL, TONE_AUDIO_END_MAX, TONE_AUDIO_TRUNCATED = 1, 2, 4, 8
+TONE_AUDIO_END = TONE_AUDIO_END_TAIL | TONE_AUDIO_END_MAX
+TONE_AUDIO_CHUNK_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("kind", "<u4"), ("reserved", "<u4"),
+                                   ("sample_counter", "<u8"), ("n_samples", "<u8"), ("tone_start", "<u8"), ("samples", "<u8")])
+assert TONE_AUDIO_CHUNK_DTYPE.itemsize == 48
+
+
+def tone_audio_chunk_bound(n_blocks: int) -> int:
+    """SAME_TONE_AUDIO_CHUNK_BOUND: the chunks of a channel in a call in which it completes n_blocks"""
+    return 1 + (int(n_blocks) + 28) // 30 + (int(n_blocks) + 26) // 30
 
 
 def block_length(rate: int) -> int:
@@ -67,6 +83,10 @@ def _lib() -> C.CDLL:
     sig("same_tones_poll", C.c_int, vp, vp, C.c_size_t, P(C.c_size_t), P(C.c_size_t))
     sig("same_tones_reset_channels", C.c_int, vp, P(u32), C.c_size_t)
     sig("same_tones_channel_sample_counter", u64, vp, u32)
+    sig("same_tone_audio_set", C.c_int, vp, u32, u32, u32, C.c_size_t)
+    sig("same_tone_audio_peek", C.c_int, vp, P(vp), P(C.c_size_t))
+    sig("same_tone_audio_drop", C.c_int, vp, C.c_size_t)
+    sig("same_tone_audio_chunk_bound", u32, u32)
     _declared = True
     return L
 
@@ -193,6 +213,31 @@ class ToneDetector:
             if left.value == 0 or n.value == 0:
                 break
         return np.concatenate(parts) if parts else np.zeros(0, dtype=TONE_EVENT_DTYPE)
+
+    def set_audio_capture(self, kinds: int, tail_blocks: int, max_blocks: int, samples_per_call: int) -> None:
+        """Tone alert (same_tone_audio_set): capture what follows a confirmed tone of `kinds` (a mask of TONE_ATTENTION |
+        TONE_WAT) until no enabled tone has been active for `tail_blocks` blocks more, `max_blocks` blocks at the most.  Before
+        the detector's first sample.  `samples_per_call`: the pool of one call (three are allocated on the device now); 0 turns
+        capture off."""
+        _check(self._L.same_tone_audio_set(self._h, int(kinds), int(tail_blocks), int(max_blocks), int(samples_per_call)))
+
+    def poll_audio(self) -> list:
+        """The queued audio chunks of the calls that have passed, which are then dropped: (record, samples) pairs, the record a
+        TONE_AUDIO_CHUNK_DTYPE scalar (its `samples` field is 0) and the samples an owned float32 array.  Calls in call order;
+        inside a call by channel, then by sample_counter.  `sync()` first to include the calls in flight."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _check(self._L.same_tone_audio_peek(self._h, C.byref(ptr), C.byref(n)))
+        out = []
+        if n.value:
+            raw = (C.c_char * (n.value * TONE_AUDIO_CHUNK_DTYPE.itemsize)).from_address(ptr.value)
+            recs = np.frombuffer(raw, dtype=TONE_AUDIO_CHUNK_DTYPE).copy()
+            for r in recs:
+                k = int(r["n_samples"])
+                a = np.ctypeslib.as_array(C.cast(int(r["samples"]), C.POINTER(C.c_float)), shape=(k,)).copy() if k else np.zeros(0, np.float32)
+                r["samples"] = 0
+                out.append((r, a))
+            _check(self._L.same_tone_audio_drop(self._h, n.value))
+        return out
 
     def reset_channels(self, channels) -> None:
         """The listed channels start again at this point of the stream (same_tones_reset_channels).  An active tone emits no

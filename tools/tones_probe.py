@@ -8,8 +8,17 @@ detector's own sync included, so the copy of the event slots and their harvest a
   - relaxed_ms:  the relaxed batch's own call on the same buffer in the same run, its sync and event poll included.
 One JSON line per combination; --out FILE also writes them there.
 
+--capture measures tone-alert audio (include/same_tone_audio.h) instead: whole-call times by the same
+protocol, of variants alternated in one run, --repeats times each for the spread.  At 32 768 channels x 2 s, both layouts, f32
+and int16: a handle with capture off ("off"), one with capture on and nothing open ("quiet": the AFSK workload holds no tone),
+one with a 1050 Hz tone on every 64th channel ("one_in_64", capture off and on).  At 4 096 x 2 s: the tone on every channel
+("all", capture off and on).  Each handle is first fed 2 s of its input, so that its captures are open (max_blocks is out of
+reach) and every timed call copies every row of its tone channels, on the device and then to the host: a call's time has its
+process call and a same_tone_audio_peek / same_tone_audio_drop of what has arrived, the samples' way to the host included.
+
 For the kernels' own time, run one combination under rocprofv3 --kernel-trace --stats, e.g.
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/tones_probe.py --shapes 32768x2 --layouts time --samples f32 --no-batch
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/tones_probe.py --capture --shapes 4096x2 --layouts time --samples f32 --repeats 1
 """
 import argparse
 import json
@@ -32,6 +41,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-batch", action="store_true", help="leave out the relaxed batch's call")
     ap.add_argument("--out", default="")
+    ap.add_argument("--capture", action="store_true", help="measure tone-alert audio instead (see above)")
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
     import torch
     import sameold_amd as sa
@@ -51,7 +62,67 @@ def main():
         return (time.perf_counter() - t0) * 1e3 / a.calls
 
     lines = []
-    for shape in a.shapes.split(","):
+    if a.capture:
+        import ctypes
+        import math
+        import numpy as np
+        for shape in (a.shapes if a.shapes != ap.get_default("shapes") else "32768x2,4096x2").split(","):
+            n_ch, seconds = (int(v) for v in shape.split("x"))
+            n = RATE * seconds
+            quiet = sa.synth_afsk(n_ch, n, RATE, seed=3, noise_sigma=0.05)          # [n, C] float32
+            # a 1050 Hz tone that is continuous from call to call (n is a whole number of seconds)
+            tone = (8000.0 * torch.sin(2.0 * math.pi * 1050.0 / RATE * torch.arange(n, dtype=torch.float64, device="cuda"))).round().to(torch.float32)
+            every = 64 if n_ch > 4096 else 1
+            loud = quiet.clone()
+            loud[:, ::every] = tone[:, None]
+            captured = (n_ch + every - 1) // every * n
+            for layout_name in a.layouts.split(","):
+                layout = sa.LAYOUT_TIME_MAJOR if layout_name == "time" else sa.LAYOUT_CHANNEL_MAJOR
+                for sample in a.samples.split(","):
+                    def tensor(base):
+                        x = base if layout == sa.LAYOUT_TIME_MAJOR else base.T.contiguous()
+                        return x.round().clamp(-32768, 32767).to(torch.int16) if sample == "i16" else x
+                    xq, xl = tensor(quiet), tensor(loud)
+                    name = "one_in_64" if every == 64 else "all"
+                    variants = ([("off", xq, False), ("quiet", xq, True)] if every == 64 else []) + [(name + "_off", xl, False), (name + "_on", xl, True)]
+                    times = {v[0]: [] for v in variants}
+                    chunks = {}
+                    for _ in range(a.repeats):
+                        for vname, x, on in variants:              # alternated: every repeat runs every variant
+                            td = sa.ToneDetector(n_ch, RATE)
+                            if on:
+                                td.set_audio_capture(sa.TONE_WAT | sa.TONE_ATTENTION, 3, 1 << 30, captured)
+                            td.process(x, None, layout)            # (the tone is confirmed: captures are open from here on)
+                            td.sync()
+                            td.poll_audio()
+
+                            def take():                            # the chunks that have arrived leave the queue, uncopied
+                                ptr, k = ctypes.c_void_p(), ctypes.c_size_t()
+                                assert td._L.same_tone_audio_peek(td._h, ctypes.byref(ptr), ctypes.byref(k)) == 0
+                                if k.value:
+                                    recs = np.frombuffer((ctypes.c_char * (k.value * 48)).from_address(ptr.value), dtype=sa.TONE_AUDIO_CHUNK_DTYPE)
+                                    chunks[vname] = int(recs["n_samples"].sum()) // max(1, len(set(recs["sample_counter"].tolist())))
+                                    assert td._L.same_tone_audio_drop(td._h, k.value) == 0
+
+                            def call():
+                                td.process(x, None, layout)
+                                if on:
+                                    take()
+
+                            def drain():
+                                td.sync()
+                                if on:
+                                    take()
+                            times[vname].append(round(timed(call, drain), 3))
+                            del td
+                    line = {"channels": n_ch, "seconds": seconds, "layout": layout_name, "sample": sample, "calls": a.calls,
+                            "ms": times, "captured_samples_of_the_last_call": chunks,
+                            "copy_bytes_per_call": {name: captured * ((2 if sample == "i16" else 4) + 4)}}
+                    print(json.dumps(line), flush=True)
+                    lines.append(line)
+                    del xq, xl
+            del quiet, loud
+    for shape in ([] if a.capture else a.shapes.split(",")):
         n_ch, seconds = (int(v) for v in shape.split("x"))
         n = RATE * seconds
         base = sa.synth_afsk(n_ch, n, RATE, seed=3, noise_sigma=0.05)          # [n, C] float32
