@@ -19,5 +19,5 @@ from .tones import (  # noqa: F401
     TONE_ATTENTION_EACH_SHARE, TONE_ATTENTION_SUM_SHARE, TONE_END_BLOCKS, TONE_EVENT_DTYPE, TONE_START_BLOCKS, TONE_WAT_SHARE,
     block_length,
     TONE_AUDIO_CHUNK_DTYPE, TONE_AUDIO_END, TONE_AUDIO_END_MAX, TONE_AUDIO_END_TAIL, TONE_AUDIO_FIRST, TONE_AUDIO_TRUNCATED,
-    tone_audio_chunk_bound,
+    tone_audio_chunk_bound, TONE_DELIVERY_CHUNK_DTYPE,
 )

@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 # product's -- build/name/, libsame_rx.name.so -- and tools load it with SAME_LIB_VARIANT=name; the product never reads either.
 VARIANT = os.environ.get("SAME_BUILD_VARIANT", "")
 LIB = os.path.join(HERE, f"libsame_rx.{VARIANT}.so" if VARIANT else "libsame_rx.so")
-SOURCES = ["same_kernels.hip", "same_kernels_fast.hip", "same_kernels_pipe.hip", "same_kernels_relaxed.hip", "same_kernels_sym.hip", "same_kernels_sym_hi.hip", "same_synth.hip", "same_transport.hip", "same_capture.hip", "same_resample.hip", "same_tones.hip", "same_tone_audio.hip", "same_batch.cpp", "same_harvest.cpp", "same_select.cpp", "same_tp_plan.cpp", "same_config.cpp", "same_transport.cpp", "same_place.cpp"]
+SOURCES = ["same_kernels.hip", "same_kernels_fast.hip", "same_kernels_pipe.hip", "same_kernels_relaxed.hip", "same_kernels_sym.hip", "same_kernels_sym_hi.hip", "same_synth.hip", "same_transport.hip", "same_capture.hip", "same_resample.hip", "same_tones.hip", "same_tone_audio.hip", "same_tone_delivery.hip", "same_batch.cpp", "same_harvest.cpp", "same_select.cpp", "same_tp_plan.cpp", "same_config.cpp", "same_transport.cpp", "same_place.cpp"]
 # flags of one source only.  same_kernels_sym_hi.hip (the symbol-paced pipeline at 44.1 / 48 kHz, six wavefronts per CU): the
 # machine scheduler set for instruction-level parallelism -- 3.3-3.6 % faster there with the same events; the 22.05 kHz unit
 # (twelve wavefronts per CU) measured up to 10 % SLOWER with it and keeps the default (same_kernels_sym.hip, SYM_SPLIT_TU)
@@ -29,7 +29,7 @@ SOURCES = ["same_kernels.hip", "same_kernels_fast.hip", "same_kernels_pipe.hip",
 # operations and their order are the source's either way (-ffp-contract=off: the scheduler reorders, it does not reassociate)
 SOURCE_FLAGS = {"same_kernels_sym_hi.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "same_kernels_pipe.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-HEADERS = ["same_dev_common.h", "same_fast_common.h", "same_relaxed_common.h", "same_pipe_common.h", "same_profile.h", "same_device.h", "same_hipmem.h", "same_launch.h", "same_select.h", "same_tp_plan.h", "same_config.h", "same_transport.h", "same_transport_dev.h", "same_capture_dev.h", "same_resets.h", "same_harvest.h", "same_resample_dev.h", "same_resample_plan.h", "same_tones_dev.h", "same_tones_plan.h", "same_tone_audio_dev.h", "same_tone_audio_plan.h", "same_tone_audio_kernels.h", "../../include/same_rx.h", "../../include/same_resample.h", "../../include/same_tones.h", "../../include/same_tone_audio.h",
+HEADERS = ["same_dev_common.h", "same_fast_common.h", "same_relaxed_common.h", "same_pipe_common.h", "same_profile.h", "same_device.h", "same_hipmem.h", "same_launch.h", "same_select.h", "same_tp_plan.h", "same_config.h", "same_transport.h", "same_transport_dev.h", "same_capture_dev.h", "same_resets.h", "same_harvest.h", "same_resample_dev.h", "same_resample_plan.h", "same_tones_dev.h", "same_tones_plan.h", "same_tone_audio_dev.h", "same_tone_audio_plan.h", "same_tone_audio_kernels.h", "same_tone_delivery_dev.h", "same_tone_delivery_plan.h", "same_tone_delivery_kernels.h", "../../include/same_rx.h", "../../include/same_resample.h", "../../include/same_tones.h", "../../include/same_tone_audio.h", "../../include/same_tone_delivery.h",
            "../../include/same_place.h", "samedec_main.cpp"]
 SAMEDEC = os.path.join(HERE, "samedec_gpu")      # the command-line decoder (host-only program, dlopens LIB)
 ARCH = "gfx950"

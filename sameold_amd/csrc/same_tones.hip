@@ -22,6 +22,10 @@
 // tones_sm_kernel, the capture-aware state-machine kernel, the prefix kernel and the layout's copy kernel of same_tone_audio.hip,
 // and copies the call's chunk records behind its event slots.  The samples stay in the slot's pool on the device until the
 // call has passed and someone asks for them (fetch_block): same_tone_audio_peek, or the call that takes the slot next.
+// Delivery form (include/same_tone_delivery.h): a handle in delivery mode queues, behind that capture work, the
+// output-offset kernel, the decimator and the history kernel of same_tone_delivery.hip.  The float pool is then a staging buffer
+// that stays on the device; what fetch_block copies is the used part of the slot's int16 delivery pool, into a pinned host
+// block that returns to a free list when its last chunk has been dropped.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -33,10 +37,13 @@
 #include <vector>
 
 #include "../../include/same_tone_audio.h"
+#include "../../include/same_tone_delivery.h"
 #include "../../include/same_tones.h"
 #include "same_hipmem.h"
 #include "same_tone_audio_kernels.h"
 #include "same_tone_audio_plan.h"
+#include "same_tone_delivery_kernels.h"
+#include "same_tone_delivery_plan.h"
 #include "same_tones_plan.h"
 
 namespace same {
@@ -174,6 +181,7 @@ size_t events_offset(uint32_t n_channels) { return (((size_t)n_channels * sizeof
 // the samples of one call, on the host once fetched
 struct AudioBlock {
     std::vector<float> data;
+    same::PinnedBuf<int16_t> pcm;                // delivery mode: the call's delivered samples, pinned; back to free_pcm behind the last drop
     size_t chunks = 0;                           // queued chunks of the call that have not been dropped
     uint64_t used = 0;                           // samples of the call's pool in use
     int slot = -1;                               // the slot whose pool holds them until they are fetched; -1: fetched
@@ -196,6 +204,8 @@ struct same_tones {
         // tone-alert audio: the call's chunk records, its sample pool, and the host block that still waits for the pool's samples
         same::PinnedBuf<uint8_t> cap_out;
         same::DevBuf<float> pool;
+        same::DevBuf<int16_t> dpool;             // delivery mode: the call's delivery pool (pool is then the staging buffer)
+        size_t outs_offset = 0;                  // delivery mode: where the call's output records lie in cap_out
         bool captures = false;                   // the call in this slot ran with capture on
         AudioBlock *unfetched = nullptr;
     };
@@ -216,6 +226,15 @@ struct same_tones {
     std::vector<same_tone_audio_chunk> pending;  // chunks of harvested calls (samples: the offset in the call's pool) ...
     std::vector<same_tone_audio_chunk> ready;    // ... and, from ready_head on, the view same_tone_audio_peek hands out
     size_t ready_head = 0;
+
+    // delivery form: the ratio and taps, the channels' histories and capture-local clocks, and the queue in its own record
+    same::ToneDeliveryPlan delivery;
+    same::DevBuf<float> d_taps_t;                // [T][L]
+    same::DevBuf<float> d_hist;                  // [C][T - 1]
+    same::DevBuf<uint64_t> d_anext;              // [C]
+    std::vector<same::PinnedBuf<int16_t>> free_pcm;   // host blocks whose chunks have all been dropped, at most kSlots + 1
+    std::vector<same_tone_delivery_chunk> dpending, dready;
+    size_t dready_head = 0;
 };
 
 namespace same {
@@ -241,11 +260,19 @@ void harvest(same_tones *h, same_tones::Slot &s)
     const uint32_t *n_spans = (const uint32_t *)(s.cap_out.get() + kCapHeaderBytes);
     const uint8_t *spans = s.cap_out.get() + cap_spans_offset(C);
     const uint32_t *span_off = (const uint32_t *)(s.desc.get() + C);
+    const bool delivery = h->delivery.on();
     size_t n = 0;
     for (uint32_t c = 0; c < C; ++c)
         for (uint32_t i = 0; i < n_spans[c]; ++i, ++n) {
             tn::Span sp;
             std::memcpy(&sp, spans + ((size_t)span_off[c] + i) * sizeof(tn::Span), sizeof(sp));
+            if (delivery) {
+                td::Out o;
+                std::memcpy(&o, s.cap_out.get() + s.outs_offset + ((size_t)span_off[c] + i) * sizeof(td::Out), sizeof(o));
+                h->dpending.push_back(same_tone_delivery_chunk{sp.channel, sp.flags, sp.kind, h->delivery.params.rate, sp.sample_counter, o.out_index,
+                                                               o.n_out, sp.tone_start, (const int16_t *)(uintptr_t)(o.off * sizeof(int16_t))});
+                continue;
+            }
             h->pending.push_back(same_tone_audio_chunk{sp.channel, sp.flags, sp.kind, 0, sp.sample_counter, sp.n, sp.tone_start,
                                                        (const float *)(uintptr_t)(sp.off * sizeof(float))});
         }
@@ -253,7 +280,7 @@ void harvest(same_tones *h, same_tones::Slot &s)
     h->blocks.emplace_back();
     AudioBlock &b = h->blocks.back();
     b.chunks = n;
-    b.used = header[1];
+    b.used = delivery ? header[2] : header[1];
     if (b.used) { b.slot = (int)(&s - h->slot); s.unfetched = &b; }
 }
 
@@ -262,6 +289,22 @@ int fetch_block(same_tones *h, AudioBlock &b)
 {
     if (b.slot < 0) return SAME_OK;
     same_tones::Slot &s = h->slot[b.slot];
+    if (h->delivery.on()) {
+        // a free block with room, else any free block (it grows), else a new one; sizes in steps of 64 Ki samples
+        size_t pick = h->free_pcm.size();
+        for (size_t i = 0; i < h->free_pcm.size(); ++i)
+            if (h->free_pcm[i].size() >= b.used) { pick = i; break; }
+        if (pick == h->free_pcm.size() && pick) pick -= 1;
+        if (pick < h->free_pcm.size()) { b.pcm = std::move(h->free_pcm[pick]); h->free_pcm.erase(h->free_pcm.begin() + (ptrdiff_t)pick); }
+        const hipError_t e = b.pcm.ensure(((size_t)b.used + 0xffff) & ~(size_t)0xffff);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "%llu delivered samples on the host: %s", (unsigned long long)b.used, hipGetErrorString(e));
+        TN_HIP_TRY(hipMemcpyAsync(b.pcm.get(), s.dpool.get(), (size_t)b.used * sizeof(int16_t), hipMemcpyDeviceToHost, h->copy_stream));
+        TN_HIP_TRY(hipStreamSynchronize(h->copy_stream));
+        b.slot = -1;
+        s.unfetched = nullptr;
+        return SAME_OK;
+    }
     try { b.data.resize((size_t)b.used); } catch (...) { return fail(SAME_ENOMEM, "%llu captured samples on the host", (unsigned long long)b.used); }
     TN_HIP_TRY(hipMemcpyAsync(b.data.data(), s.pool.get(), (size_t)b.used * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
     TN_HIP_TRY(hipStreamSynchronize(h->copy_stream));
@@ -326,7 +369,10 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
     uint64_t cap_bytes = 0;
     if (capture) {
         if (s.unfetched && (rc = fetch_block(h, *s.unfetched))) return rc;
-        cap_bytes = cap_spans_offset(C) + ToneAudioPlan::describe(s.desc.get(), C, (uint32_t *)(s.desc.get() + C)) * sizeof(tn::Span);
+        const uint64_t slots = ToneAudioPlan::describe(s.desc.get(), C, (uint32_t *)(s.desc.get() + C));
+        cap_bytes = cap_spans_offset(C) + slots * sizeof(tn::Span);
+        s.outs_offset = (size_t)cap_bytes;        // (a multiple of 16: the output records are aligned)
+        if (h->delivery.on()) cap_bytes += slots * sizeof(td::Out);
         if (cap_bytes > kMaxCallBytes) return fail(SAME_ENOMEM, "the call needs %llu bytes of chunk slots; nothing was consumed", (unsigned long long)cap_bytes);
         e = h->d_cap_out.ensure((size_t)cap_bytes);
         if (e == hipSuccess) e = s.cap_out.ensure((size_t)cap_bytes);
@@ -353,6 +399,15 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
                               h->plan.coef.N, C};
         TN_HIP_TRY(tone_audio_launch_sm(k, stream));
         TN_HIP_TRY(tone_audio_launch_copy(k, d_x, n_rows, layout, stream));
+        if (h->delivery.on()) {
+            const td::Params &p = h->delivery.params;
+            // a chunk has at most n_rows placed rows: its outputs, in tiles of 256
+            const uint64_t most = rs::outputs_after(n_rows, p.L, p.M) + 1;
+            const ToneDeliveryCall dk{p, h->d_taps_t.get(), h->d_hist.get(), h->d_anext.get(), s.dpool.get(), s.outs_offset,
+                                      (uint32_t)((most + td::kTileOutputs - 1) / td::kTileOutputs)};
+            TN_HIP_TRY(tone_delivery_launch(k, dk, stream));
+            TN_HIP_TRY(tone_delivery_launch_history(k, dk, d_x, n_rows, layout, stream));
+        }
         TN_HIP_TRY(hipMemcpyAsync(s.cap_out.get(), h->d_cap_out.get(), (size_t)cap_bytes, hipMemcpyDeviceToHost, stream));
     } else {
         hipLaunchKernelGGL(tones_sm_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, h->d_desc.get(), h->plan.coef.N, h->d_qual.get(),
@@ -431,7 +486,10 @@ int same_tone_audio_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, uin
         return fail(SAME_EINVAL, "kinds = %u is not a non-zero mask of SAME_TONE_ATTENTION | SAME_TONE_WAT, or max_blocks = %u is zero", kinds, max_blocks);
     TN_HIP_TRY(hipSetDevice(h->device));
     h->audio = ToneAudioPlan();                   // (off until everything is there)
+    h->delivery = ToneDeliveryPlan();             // (the float mode, or none: not the delivery form)
     hipError_t e = hipSuccess;
+    for (same_tones::Slot &s : h->slot)
+        if (e == hipSuccess) e = s.dpool.reset();
     if (!plan.on()) {
         for (same_tones::Slot &s : h->slot)
             if (e == hipSuccess) e = s.pool.reset();
@@ -467,6 +525,7 @@ int same_tone_audio_peek(same_tones *h, const same_tone_audio_chunk **chunks, si
     TN_HIP_TRY(hipSetDevice(h->device));
     int rc = collect(h, false);
     if (rc) return rc;
+    if (h->delivery.on()) return SAME_OK;         // (its chunks are same_tone_delivery_peek's)
     if (h->ready_head == h->ready.size()) { h->ready.clear(); h->ready_head = 0; }
     // the harvested calls' samples come to the host, and their chunks into the view
     size_t at = 0;
@@ -500,6 +559,92 @@ int same_tone_audio_drop(same_tones *h, size_t n)
         b.chunks -= k;
         n -= k;
         if (b.chunks == 0) h->blocks.pop_front();
+    }
+    return SAME_OK;
+}
+
+int same_tone_delivery_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, uint32_t max_blocks, size_t samples_per_call, uint32_t out_rate,
+                           float gain)
+{
+    if (!h) return fail(SAME_EINVAL, "null handle");
+    if (h->fed) return fail(SAME_EINVAL, "delivery is set before the handle's first sample");
+    ToneDeliveryPlan plan;
+    const int prc = plan.set(kinds, tail_blocks, max_blocks, samples_per_call, h->plan.rate, out_rate, gain);
+    if (prc == SAME_ERATE) return fail(prc, "%u -> %u Hz needs more than %u phases or %u taps", h->plan.rate, out_rate, rs::kMaxL, rs::kMaxT);
+    if (prc)
+        return fail(prc, "kinds = %u is not a non-zero mask of SAME_TONE_ATTENTION | SAME_TONE_WAT, max_blocks = %u is zero, gain = %g is not finite and "
+                         "positive, or out_rate = %u is zero or above the handle's %u Hz", kinds, max_blocks, (double)gain, out_rate, h->plan.rate);
+    // the float path's memory first: the staging pools and the capture state (this also leaves the delivery form off)
+    const int rc = same_tone_audio_set(h, kinds, tail_blocks, max_blocks, samples_per_call);
+    if (rc || !plan.on()) return rc;
+    h->audio = ToneAudioPlan();                   // (off until everything is there)
+    const uint32_t C = h->plan.n_channels();
+    const td::Params &p = plan.params;
+    hipError_t e = h->d_taps_t.ensure(plan.taps_t.size());
+    if (e == hipSuccess) e = h->d_hist.ensure((size_t)C * (p.T - 1) + 1);
+    if (e == hipSuccess) e = h->d_anext.ensure(C);
+    // L <= M: a call delivers no more samples than it placed rows, so samples_per_call int16 cannot overflow
+    for (same_tones::Slot &s : h->slot)
+        if (e == hipSuccess) e = s.dpool.ensure(samples_per_call);
+    if (e == hipSuccess) e = hipMemcpy(h->d_taps_t.get(), plan.taps_t.data(), plan.taps_t.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(h->d_anext.get(), 0, (size_t)C * sizeof(uint64_t));
+    if (e != hipSuccess) {
+        for (same_tones::Slot &s : h->slot) { (void)s.pool.reset(); (void)s.dpool.reset(); }
+        return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the delivery pools (3 x %zu samples) failed: %s; capture is off",
+                    samples_per_call, hipGetErrorString(e));
+    }
+    h->audio = plan.audio;
+    h->delivery = std::move(plan);
+    return SAME_OK;
+}
+
+int same_tone_delivery_peek(same_tones *h, const same_tone_delivery_chunk **chunks, size_t *n)
+{
+    if (!h || !chunks || !n) return fail(SAME_EINVAL, "null argument");
+    *chunks = nullptr;
+    *n = 0;
+    TN_HIP_TRY(hipSetDevice(h->device));
+    int rc = collect(h, false);
+    if (rc) return rc;
+    if (!h->delivery.on()) return SAME_OK;
+    if (h->dready_head == h->dready.size()) { h->dready.clear(); h->dready_head = 0; }
+    // the harvested calls' samples come to the host, and their chunks into the view
+    size_t at = 0;
+    for (AudioBlock &b : h->blocks) {
+        if (b.published) continue;
+        if ((rc = fetch_block(h, b))) break;
+        try { h->dready.reserve(h->dready.size() + b.chunks); } catch (...) { rc = fail(SAME_ENOMEM, "delivery view"); break; }
+        for (size_t i = 0; i < b.chunks; ++i) {
+            same_tone_delivery_chunk ch = h->dpending[at + i];
+            ch.samples = ch.n_samples ? b.pcm.get() + (uintptr_t)ch.samples / sizeof(int16_t) : nullptr;
+            h->dready.push_back(ch);
+        }
+        at += b.chunks;
+        b.published = true;
+    }
+    h->dpending.erase(h->dpending.begin(), h->dpending.begin() + (ptrdiff_t)at);
+    if (rc) return rc;
+    *n = h->dready.size() - h->dready_head;
+    *chunks = *n ? h->dready.data() + h->dready_head : nullptr;
+    return SAME_OK;
+}
+
+int same_tone_delivery_drop(same_tones *h, size_t n)
+{
+    if (!h) return fail(SAME_EINVAL, "null argument");
+    if (n > h->dready.size() - h->dready_head) return fail(SAME_EINVAL, "more chunks than the view holds");
+    h->dready_head += n;
+    while (n) {                                   // (the view's chunks are those of the oldest blocks)
+        AudioBlock &b = h->blocks.front();
+        const size_t k = n < b.chunks ? n : b.chunks;
+        b.chunks -= k;
+        n -= k;
+        if (b.chunks) continue;
+        // the block's memory is recycled: pinning it again for every call would cost more than the copy
+        if (b.pcm.get() && h->free_pcm.size() <= (size_t)kSlots) {
+            try { h->free_pcm.push_back(std::move(b.pcm)); } catch (...) { }
+        }
+        h->blocks.pop_front();
     }
     return SAME_OK;
 }

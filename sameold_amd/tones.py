@@ -9,7 +9,9 @@ a batch reads and reports tone events that count in each channel's own samples.
 
 Tone alert (include/same_tone_audio.h): `td.set_audio_capture(TONE_WAT | TONE_ATTENTION, tail_blocks, max_blocks,
 samples_per_call)` before the first sample makes the same `process` calls copy what follows a confirmed tone out of `x` on the
-device; `td.sync(); td.poll_audio()` hands the chunks out.
+device; `td.sync(); td.poll_audio()` hands the chunks out.  In delivery form (include/same_tone_delivery.h):
+`td.set_audio_delivery(kinds, tail_blocks, max_blocks, samples_per_call, out_rate, gain)` instead, and `td.poll_delivery()` hands
+out int16 at `out_rate`, decimated and quantised on the device.
 
 There is no CPU fallback: the detection runs in the library's gfx950 kernels or not at all.
 """
@@ -41,6 +43,10 @@ TONE_AUDIO_END = TONE_AUDIO_END_TAIL | TONE_AUDIO_END_MAX
 TONE_AUDIO_CHUNK_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("kind", "<u4"), ("reserved", "<u4"),
                                    ("sample_counter", "<u8"), ("n_samples", "<u8"), ("tone_start", "<u8"), ("samples", "<u8")])
 assert TONE_AUDIO_CHUNK_DTYPE.itemsize == 48
+# the delivery form (include/same_tone_delivery.h): same_tone_delivery_chunk
+TONE_DELIVERY_CHUNK_DTYPE = np.dtype([("channel", "<u4"), ("flags", "<u4"), ("kind", "<u4"), ("rate", "<u4"), ("sample_counter", "<u8"),
+                                      ("out_index", "<u8"), ("n_samples", "<u8"), ("tone_start", "<u8"), ("samples", "<u8")])
+assert TONE_DELIVERY_CHUNK_DTYPE.itemsize == 56
 
 
 def tone_audio_chunk_bound(n_blocks: int) -> int:
@@ -87,6 +93,9 @@ def _lib() -> C.CDLL:
     sig("same_tone_audio_peek", C.c_int, vp, P(vp), P(C.c_size_t))
     sig("same_tone_audio_drop", C.c_int, vp, C.c_size_t)
     sig("same_tone_audio_chunk_bound", u32, u32)
+    sig("same_tone_delivery_set", C.c_int, vp, u32, u32, u32, C.c_size_t, u32, C.c_float)
+    sig("same_tone_delivery_peek", C.c_int, vp, P(vp), P(C.c_size_t))
+    sig("same_tone_delivery_drop", C.c_int, vp, C.c_size_t)
     _declared = True
     return L
 
@@ -237,6 +246,32 @@ class ToneDetector:
                 r["samples"] = 0
                 out.append((r, a))
             _check(self._L.same_tone_audio_drop(self._h, n.value))
+        return out
+
+    def set_audio_delivery(self, kinds: int, tail_blocks: int, max_blocks: int, samples_per_call: int, out_rate: int, gain: float = 1.0) -> None:
+        """Tone alert in delivery form (same_tone_delivery_set), in place of `set_audio_capture` and under its rules: the same
+        captures, handed out by `poll_delivery` as int16 at `out_rate` (at most the detector's rate; a ratio the resampler refuses
+        raises SAME_ERATE), each sample the resampler's f32 sum times `gain`, rounded to nearest even and clamped.
+        `samples_per_call` counts captured source samples; 0 turns capture off."""
+        _check(self._L.same_tone_delivery_set(self._h, int(kinds), int(tail_blocks), int(max_blocks), int(samples_per_call), int(out_rate),
+                                              float(gain)))
+
+    def poll_delivery(self) -> list:
+        """The queued delivery chunks of the calls that have passed, which are then dropped: (record, samples) pairs, the record a
+        TONE_DELIVERY_CHUNK_DTYPE scalar (its `samples` field is 0) and the samples an owned int16 array.  The order is
+        `poll_audio`'s.  `sync()` first to include the calls in flight.  Empty on a detector that is not in delivery form."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _check(self._L.same_tone_delivery_peek(self._h, C.byref(ptr), C.byref(n)))
+        out = []
+        if n.value:
+            raw = (C.c_char * (n.value * TONE_DELIVERY_CHUNK_DTYPE.itemsize)).from_address(ptr.value)
+            recs = np.frombuffer(raw, dtype=TONE_DELIVERY_CHUNK_DTYPE).copy()
+            for r in recs:
+                k = int(r["n_samples"])
+                a = np.ctypeslib.as_array(C.cast(int(r["samples"]), C.POINTER(C.c_int16)), shape=(k,)).copy() if k else np.zeros(0, np.int16)
+                r["samples"] = 0
+                out.append((r, a))
+            _check(self._L.same_tone_delivery_drop(self._h, n.value))
         return out
 
     def reset_channels(self, channels) -> None:

@@ -16,9 +16,15 @@ one with a 1050 Hz tone on every 64th channel ("one_in_64", capture off and on).
 reach) and every timed call copies every row of its tone channels, on the device and then to the host: a call's time has its
 process call and a same_tone_audio_peek / same_tone_audio_drop of what has arrived, the samples' way to the host included.
 
+--delivery measures the delivery form (include/same_tone_delivery.h) by the same protocol and beside the same
+variants, alternated in the same run: "one_in_64_delivery" / "all_delivery" is a handle set with same_tone_delivery_set at
+--out-rate (8 000 Hz), gain 1, and the same samples_per_call as the float capture.  bytes_to_host_per_call: what the last timed
+call's chunks hold, 4 bytes per float sample, 2 per delivered one (chunks are packed: there is no padding).
+
 For the kernels' own time, run one combination under rocprofv3 --kernel-trace --stats, e.g.
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/tones_probe.py --shapes 32768x2 --layouts time --samples f32 --no-batch
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/tones_probe.py --capture --shapes 4096x2 --layouts time --samples f32 --repeats 1
+    rocprofv3 --kernel-trace --stats -d OUT -- python tools/tones_probe.py --delivery --shapes 4096x2 --layouts time --samples f32 --repeats 1
 """
 import argparse
 import json
@@ -42,6 +48,8 @@ def main():
     ap.add_argument("--no-batch", action="store_true", help="leave out the relaxed batch's call")
     ap.add_argument("--out", default="")
     ap.add_argument("--capture", action="store_true", help="measure tone-alert audio instead (see above)")
+    ap.add_argument("--delivery", action="store_true", help="as --capture, with the delivery form beside the float capture")
+    ap.add_argument("--out-rate", type=int, default=8000)
     ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
     import torch
@@ -62,6 +70,8 @@ def main():
         return (time.perf_counter() - t0) * 1e3 / a.calls
 
     lines = []
+    if a.delivery:
+        a.capture = True
     if a.capture:
         import ctypes
         import math
@@ -85,24 +95,34 @@ def main():
                     xq, xl = tensor(quiet), tensor(loud)
                     name = "one_in_64" if every == 64 else "all"
                     variants = ([("off", xq, False), ("quiet", xq, True)] if every == 64 else []) + [(name + "_off", xl, False), (name + "_on", xl, True)]
+                    if a.delivery:
+                        variants.append((name + "_delivery", xl, "delivery"))
                     times = {v[0]: [] for v in variants}
-                    chunks = {}
+                    chunks, to_host = {}, {}
                     for _ in range(a.repeats):
                         for vname, x, on in variants:              # alternated: every repeat runs every variant
                             td = sa.ToneDetector(n_ch, RATE)
-                            if on:
+                            deliver = on == "delivery"
+                            if deliver:
+                                td.set_audio_delivery(sa.TONE_WAT | sa.TONE_ATTENTION, 3, 1 << 30, captured, a.out_rate)
+                            elif on:
                                 td.set_audio_capture(sa.TONE_WAT | sa.TONE_ATTENTION, 3, 1 << 30, captured)
                             td.process(x, None, layout)            # (the tone is confirmed: captures are open from here on)
                             td.sync()
                             td.poll_audio()
+                            td.poll_delivery()
+                            peek = td._L.same_tone_delivery_peek if deliver else td._L.same_tone_audio_peek
+                            drop = td._L.same_tone_delivery_drop if deliver else td._L.same_tone_audio_drop
+                            rec = sa.TONE_DELIVERY_CHUNK_DTYPE if deliver else sa.TONE_AUDIO_CHUNK_DTYPE
 
                             def take():                            # the chunks that have arrived leave the queue, uncopied
                                 ptr, k = ctypes.c_void_p(), ctypes.c_size_t()
-                                assert td._L.same_tone_audio_peek(td._h, ctypes.byref(ptr), ctypes.byref(k)) == 0
+                                assert peek(td._h, ctypes.byref(ptr), ctypes.byref(k)) == 0
                                 if k.value:
-                                    recs = np.frombuffer((ctypes.c_char * (k.value * 48)).from_address(ptr.value), dtype=sa.TONE_AUDIO_CHUNK_DTYPE)
+                                    recs = np.frombuffer((ctypes.c_char * (k.value * rec.itemsize)).from_address(ptr.value), dtype=rec)
                                     chunks[vname] = int(recs["n_samples"].sum()) // max(1, len(set(recs["sample_counter"].tolist())))
-                                    assert td._L.same_tone_audio_drop(td._h, k.value) == 0
+                                    to_host[vname] = chunks[vname] * (2 if deliver else 4)
+                                    assert drop(td._h, k.value) == 0
 
                             def call():
                                 td.process(x, None, layout)
@@ -116,7 +136,7 @@ def main():
                             times[vname].append(round(timed(call, drain), 3))
                             del td
                     line = {"channels": n_ch, "seconds": seconds, "layout": layout_name, "sample": sample, "calls": a.calls,
-                            "ms": times, "captured_samples_of_the_last_call": chunks,
+                            "ms": times, "captured_samples_of_the_last_call": chunks, "bytes_to_host_per_call": to_host,
                             "copy_bytes_per_call": {name: captured * ((2 if sample == "i16" else 4) + 4)}}
                     print(json.dumps(line), flush=True)
                     lines.append(line)
