@@ -21,8 +21,15 @@
  *         a = s1*s1;  b = s2*s2;  d = c_k*s1;  e = d*s2;  P_k = (a + b) - e
  *         Em  = E - (S * S) * invN          (the block's energy without its mean)
  *         ref = Em * halfN
- *     the block qualifies as WAT        when  Em > 0 && P_2 >= 0.5f * ref;
- *     the block qualifies as ATTENTION  when  Em > 0 && P_0 >= 0.15f * ref && P_1 >= 0.15f * ref && (P_0 + P_1) >= 0.5f * ref.
+ *         live = Em > 0 && Em >= E * 0.015625f        (1/64, exact in f32: one multiply, one compare)
+ *     the block qualifies as WAT        when  live && P_2 >= 0.5f * ref;
+ *     the block qualifies as ATTENTION  when  live && P_0 >= 0.15f * ref && P_1 >= 0.15f * ref && (P_0 + P_1) >= 0.5f * ref.
+ *     The mean is taken out of the energy but not out of the three sums: 853 Hz and 960 Hz make 34.12 and 38.4 cycles in a
+ *     block, so a constant leaks into P_0 and P_1 (1050 Hz makes exactly 42 and does not leak).  On an idle channel -- a
+ *     constant, or a constant with a few counts of noise -- Em is tiny against E, and the leak alone would pass both ATTENTION
+ *     tests; `live` asks that the energy without the mean be a real share of the energy.  The limit that follows: a tone of
+ *     amplitude A on a DC offset of up to 3 A still qualifies (Em / E >= 0.027); at an offset of 5 A the two-tone
+ *     (Em / E = 0.0099) and at 6 A the 1050 Hz tone (0.0137) no longer do.
  *   - state machine, one per class and channel, independent of each other: active, run, miss, start.  It runs on the block
  *     index b (the block's first sample is b * N) with q = the block qualifies.
  *       not active:  q:  if run == 0, start = b * N;  run++;  if run == 25: active = 1, miss = 0, emit START with

@@ -27,6 +27,7 @@ constexpr uint32_t kBlocksPerSecond = 25;
 constexpr uint32_t kStartBlocks = SAME_TONES_START_BLOCKS, kEndBlocks = SAME_TONES_END_BLOCKS;
 constexpr double kToneHz[3] = {853.0, 960.0, 1050.0};
 constexpr float kWatShare = 0.5f, kAttnEachShare = 0.15f, kAttnSumShare = 0.5f;
+constexpr float kLiveShare = 0.015625f;                   // 1/64: a block is live only when Em is at least this share of E
 constexpr uint32_t kQAttention = 1u, kQWat = 2u;          // the qualify bits of a block
 
 // what a rate fixes
@@ -73,7 +74,9 @@ SAME_HD inline BlockOut finish(const Acc &acc, const Coef &cf)
     }
     o.Em = acc.E - (acc.S * acc.S) * cf.invN;
     const float ref = o.Em * cf.halfN;
-    const bool live = o.Em > 0.0f;
+    // (a constant leaks into P_0 and P_1 -- 34.12 and 38.4 cycles per block -- and on an idle channel Em is LSB noise or rounding
+    // residue, far below E: without the second test a muted channel with a DC offset qualifies as ATTENTION in every block)
+    const bool live = o.Em > 0.0f && o.Em >= acc.E * kLiveShare;
     const bool wat = live && o.P[2] >= kWatShare * ref;
     const bool attn = live && o.P[0] >= kAttnEachShare * ref && o.P[1] >= kAttnEachShare * ref && (o.P[0] + o.P[1]) >= kAttnSumShare * ref;
     o.q = (attn ? kQAttention : 0u) | (wat ? kQWat : 0u);

@@ -51,7 +51,8 @@ def captures_of_bits(attn, wat, N: int, kinds: int, tail_blocks: int, max_blocks
 def captures_of_stream(x, rate: int, kinds: int, tail_blocks: int, max_blocks: int):
     """captures_of_bits of one whole stream (1-D), with `samples`: the float32 slice of the stream, to its end for an open one"""
     N = tr.block_length(rate)
-    attn, wat = tr.qualify_f32(tr.blocks_f32(x, rate), rate)
+    vals, E = tr.blocks_f32(x, rate, True)
+    attn, wat = tr.qualify_f32(vals, rate, E)
     caps = captures_of_bits(attn, wat, N, kinds, tail_blocks, max_blocks)
     for c in caps:
         c["samples"] = np.asarray(x[c["first"]:c["end"]]).astype(np.float32)

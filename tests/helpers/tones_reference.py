@@ -10,6 +10,7 @@ ATTENTION, WAT = 1, 2
 START, END = 1, 2
 START_BLOCKS, END_BLOCKS = 25, 5
 WAT_SHARE, ATTN_EACH_SHARE, ATTN_SUM_SHARE = 0.5, 0.15, 0.5
+LIVE_SHARE = 0.015625     # 1/64, exact in f32: a block is live only when Em >= this share of E
 MIN_RATE, MAX_RATE = 8000, 96000
 
 EVENT_DTYPE = np.dtype([("channel", "<u4"), ("kind", "<u4"), ("edge", "<u4"), ("reserved", "<u4"),
@@ -35,9 +36,10 @@ def _blocks_of(x, rate):
     return x[..., : nb * N].reshape(x.shape[:-1] + (nb, N)), N
 
 
-def blocks_f32(x, rate: int) -> np.ndarray:
+def blocks_f32(x, rate: int, with_energy: bool = False):
     """P_0, P_1, P_2, Em of every whole block, float32 [..., blocks, 4], in the contract's operations and order.
-    x: float32 or int16 (converted exactly), [..., samples]."""
+    x: float32 or int16 (converted exactly), [..., samples].  with_energy: (that, E float32 [..., blocks]) -- the block's
+    energy with its mean, E = E + x * x over the block in order, which the live guard of qualify_f32 reads."""
     xb, N = _blocks_of(x, rate)
     shape = xb.shape[:-1]
     xb = xb.reshape(-1, N).astype(np.float32)
@@ -66,17 +68,21 @@ def blocks_f32(x, rate: int) -> np.ndarray:
         out[:, k] = (a + b) - e
     inv_n = np.float32(1.0) / np.float32(N)
     out[:, 3] = E - (S * S) * inv_n
-    assert out.dtype == np.float32
+    assert out.dtype == np.float32 and E.dtype == np.float32
+    if with_energy:
+        return out.reshape(shape + (4,)), E.reshape(shape)
     return out.reshape(shape + (4,))
 
 
-def qualify_f32(vals: np.ndarray, rate: int):
-    """(attention, wat) of blocks_f32's values, in float32 as the contract has it"""
+def qualify_f32(vals: np.ndarray, rate: int, E: np.ndarray):
+    """(attention, wat) of blocks_f32's values and energies (of the same streams), in float32 as the contract has it"""
     N = block_length(rate)
     half_n = np.float32(N) * np.float32(0.5)
     P0, P1, P2, Em = (vals[..., k] for k in range(4))
+    E = np.asarray(E)
+    assert E.dtype == np.float32 and E.shape == Em.shape
     ref = Em * half_n
-    live = Em > np.float32(0.0)
+    live = (Em > np.float32(0.0)) & (Em >= E * np.float32(LIVE_SHARE))
     wat = live & (P2 >= np.float32(WAT_SHARE) * ref)
     attn = (live & (P0 >= np.float32(ATTN_EACH_SHARE) * ref) & (P1 >= np.float32(ATTN_EACH_SHARE) * ref)
             & ((P0 + P1) >= np.float32(ATTN_SUM_SHARE) * ref))
@@ -100,9 +106,20 @@ def ratios_f64(x, rate: int) -> np.ndarray:
     return np.stack([np.where(ok, p / np.where(ok, ref, 1.0), 0.0) for p in P], axis=-1)
 
 
-def qualify_f64(r: np.ndarray):
-    wat = r[..., 2] >= WAT_SHARE
-    attn = (r[..., 0] >= ATTN_EACH_SHARE) & (r[..., 1] >= ATTN_EACH_SHARE) & (r[..., 0] + r[..., 1] >= ATTN_SUM_SHARE)
+def share_f64(x, rate: int) -> np.ndarray:
+    """Em / E of every whole block in float64, [..., blocks]; 0 where the block has no energy"""
+    xb, N = _blocks_of(x, rate)
+    xb = xb.astype(np.float64)
+    E = (xb * xb).sum(axis=-1)
+    Em = E - xb.sum(axis=-1) ** 2 / N
+    return np.where(E > 0.0, Em / np.where(E > 0.0, E, 1.0), 0.0)
+
+
+def qualify_f64(r: np.ndarray, share: np.ndarray):
+    """(attention, wat) of ratios_f64's ratios and share_f64's shares (of the same streams)"""
+    live = (share > 0.0) & (share >= LIVE_SHARE)
+    wat = live & (r[..., 2] >= WAT_SHARE)
+    attn = live & (r[..., 0] >= ATTN_EACH_SHARE) & (r[..., 1] >= ATTN_EACH_SHARE) & (r[..., 0] + r[..., 1] >= ATTN_SUM_SHARE)
     return attn, wat
 
 
@@ -170,7 +187,8 @@ class Channel:
 
 def events_of_stream(x, rate: int, channel: int = 0):
     """the events of one whole stream (1-D), from the f32 form"""
-    attn, wat = qualify_f32(blocks_f32(x, rate), rate)
+    vals, E = blocks_f32(x, rate, True)
+    attn, wat = qualify_f32(vals, rate, E)
     return Channel(channel, block_length(rate)).feed(attn, wat)
 
 
@@ -228,3 +246,40 @@ def message(rate: int, kind: int, seed: int, snr_db=None, clock: float = 1.0, mo
         p_tone = np.mean(parts[6] ** 2)
         x = x + rng.standard_normal(len(x)) * np.sqrt(p_tone / 10.0 ** (snr_db / 10.0))
     return (x * SCALE).astype(np.float32), tone_at, tone_len
+
+
+# ------------------------------------------------------------------------------------- idle channels and tones on an offset
+IDLE_CONSTANTS = (1, 37, 500, 12345, 30000, -30000)
+IDLE_NOISY = ((37, 0.3), (500, 0.6), (500, 2), (12345, 0.6), (12345, 60), (30000, 2), (30000, 150))
+TONE_DC = (0.3, 1.0, 3.0)                 # the offset of a tone of amplitude A, in A
+
+
+def idle_matrix(rate: int, n_blocks: int = 30):
+    """[(name, stream)]: channels on which nothing is sent -- a muted receiver behind a converter with an offset.  Integer-valued
+    float64 inside int16's range, n_blocks whole blocks each, so that f32 and int16 carry the same samples."""
+    N = block_length(rate)
+    n = n_blocks * N
+    t = np.arange(n, dtype=np.float64)
+    rng = np.random.default_rng(rate + 5)
+    out = [(f"constant {v}", np.full(n, float(v))) for v in IDLE_CONSTANTS]
+    out += [(f"{dc} + round({s} randn)", dc + np.round(s * rng.standard_normal(n))) for dc, s in IDLE_NOISY]
+    out.append(("500 + 40 sin 60 Hz", np.round(500.0 + 40.0 * np.sin(2.0 * np.pi * 60.0 * t / rate))))
+    out.append(("2000 + a count per 50 samples", 2000.0 + np.floor(t / 50.0)))
+    step = np.full(n, 500.0)
+    step[(n_blocks // 2) * N + N // 2:] = 520.0
+    out.append(("500, then 520 from the middle of a block", step))
+    out.append(("zeros", np.zeros(n)))
+    assert all(len(x) == n and np.all(x == np.round(x)) and np.abs(x).max() <= 32767 for _, x in out)
+    return [(name, x + 0.0) for name, x in out]
+
+
+def tone_on_dc_matrix(rate: int, n_blocks: int = 30):
+    """[(name, kind, stream)]: the 1050 Hz tone and the two-tone at amplitude A on an offset of 0.3 A, 1 A and 3 A, scaled to a
+    peak of 30 000 and rounded"""
+    n = n_blocks * block_length(rate)
+    out = []
+    for kind, what in ((WAT, "1050 Hz"), (ATTENTION, "two-tone")):
+        for d in TONE_DC:
+            A = 30000.0 / (1.0 + d)
+            out.append((f"{what} on {d} A", kind, np.round(tone(kind, n, rate, A) + d * A) + 0.0))
+    return out

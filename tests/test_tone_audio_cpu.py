@@ -179,7 +179,8 @@ def test_driver_equals_the_reference(exe, tmp_path_factory, kind, cut):
         ref = []
         for part in parts:
             ch.reset()
-            ref += ch.feed(*tr.qualify_f32(tr.blocks_f32(part, RATE), RATE))
+            vals, E = tr.blocks_f32(part, RATE, True)
+            ref += ch.feed(*tr.qualify_f32(vals, RATE, E))
         assert events[c] == ref, f"channel {c}"
 
 

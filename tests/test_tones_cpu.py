@@ -104,9 +104,9 @@ def reference(kind, reset_at=None):
         bl, ev = [], []
         for part in cuts:
             ch.reset()
-            v = tr.blocks_f32(part, RATE)
+            v, E = tr.blocks_f32(part, RATE, True)
             bl.append(v)
-            ev += ch.feed(*tr.qualify_f32(v, RATE))
+            ev += ch.feed(*tr.qualify_f32(v, RATE, E))
         blocks.append(np.concatenate(bl))
         events.append(ev)
     return blocks, events
@@ -190,8 +190,9 @@ def test_f32_and_float64_forms_take_the_same_decisions():
     for kind in ("f32", "i16"):
         x = STREAMS[kind]
         r = tr.ratios_f64(x, RATE)
-        a64, w64 = tr.qualify_f64(r)
-        a32, w32 = tr.qualify_f32(tr.blocks_f32(x, RATE), RATE)
+        a64, w64 = tr.qualify_f64(r, tr.share_f64(x, RATE))
+        vals, E = tr.blocks_f32(x, RATE, True)
+        a32, w32 = tr.qualify_f32(vals, RATE, E)
         far = tr.clear_of_thresholds(r)
         assert np.array_equal(a32[far], a64[far]) and np.array_equal(w32[far], w64[far])
         total += far.size
@@ -203,8 +204,8 @@ def test_f32_and_float64_forms_take_the_same_decisions():
 @pytest.mark.parametrize("name", ["npt", "two_and_two", "long_message"])
 def test_golden_recordings_hold_no_tone(name):
     pcm = np.fromfile(os.path.join(GOLDEN, f"{name}.22050.s16le.bin"), dtype="<i2")
-    vals = tr.blocks_f32(pcm, 22050)
-    attn, wat = tr.qualify_f32(vals, 22050)
+    vals, E = tr.blocks_f32(pcm, 22050, True)
+    attn, wat = tr.qualify_f32(vals, 22050, E)
     assert not attn.any() and not wat.any()
     r = tr.ratios_f64(pcm, 22050)
     print(f"{name}: {len(r)} blocks, largest ratio {r.max():.5f}")

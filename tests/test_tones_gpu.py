@@ -96,10 +96,10 @@ def ragged_case():
         k[[44 + i, 110 + i]] = N1 + 1
         k[[32, 120, RESET1]] = ROWS1
         counts.append(k)
-    whole = tr.blocks_f32(x.astype(np.float32), RATE1)       # [C, 43, 4]
+    whole, whole_E = tr.blocks_f32(x.astype(np.float32), RATE1, True)       # [C, 43, 4], [C, 43]
     reset_at = 3 * ROWS1                                     # RESET1 is reset between calls 2 and 3, counted from 0
-    after = tr.blocks_f32(x[RESET1, reset_at:].astype(np.float32), RATE1)
-    return x, counts, whole, reset_at, after
+    after, after_E = tr.blocks_f32(x[RESET1, reset_at:].astype(np.float32), RATE1, True)
+    return x, counts, (whole, whole_E), reset_at, (after, after_E)
 
 
 VARIANTS = {
@@ -114,7 +114,7 @@ VARIANTS = {
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_kernels_equal_the_reference_bit_for_bit(sa, ragged_case, variant):
     import torch
-    x, counts, whole, reset_at, after = ragged_case
+    x, counts, (whole, whole_E), reset_at, (after, after_E) = ragged_case
     td = sa.ToneDetector(C1, RATE1)
     assert td.block_length == N1 and np.array_equal(td.coefficients().view(np.uint32), tr.coefficients(RATE1).view(np.uint32))
     done = np.zeros(C1, np.int64)
@@ -153,14 +153,14 @@ def test_kernels_equal_the_reference_bit_for_bit(sa, ragged_case, variant):
         ch = tr.Channel(c, N1)
         if c == RESET1:
             ref = np.concatenate([whole[c, :reset_at // N1], after])
-            ref_ev = ch.feed(*tr.qualify_f32(ref[:reset_at // N1], RATE1))
+            ref_ev = ch.feed(*tr.qualify_f32(ref[:reset_at // N1], RATE1, whole_E[c, :reset_at // N1]))
             ch.reset()
-            ref_ev += ch.feed(*tr.qualify_f32(after, RATE1))
+            ref_ev += ch.feed(*tr.qualify_f32(after, RATE1, after_E))
             assert td.channel_sample_counter(c) == done[c] - reset_at
             assert [(e[1], e[2]) for e in ref_ev] == [(tr.WAT, tr.START)]                           # no END behind the reset
         else:
             ref = whole[c, :done[c] // N1]
-            ref_ev = ch.feed(*tr.qualify_f32(ref, RATE1))
+            ref_ev = ch.feed(*tr.qualify_f32(ref, RATE1, whole_E[c, :done[c] // N1]))
             assert td.channel_sample_counter(c) == done[c]
         assert mine.shape == ref.shape
         assert np.array_equal(mine.view(np.uint32), ref.view(np.uint32)), f"{variant}: channel {c}"
