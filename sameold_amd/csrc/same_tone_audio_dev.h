@@ -143,4 +143,12 @@ SAME_HD inline void span_place(Span &s, uint64_t base, uint64_t pool_cap)
 }
 
 }  // namespace tn
+
+// where a call's chunk records lie, on the device and in the pinned copy: a header of uint64 words (captured samples of the
+// call; samples of the float pool in use; in delivery mode the delivered samples, the delivery pool's use), the channels' chunk
+// counts padded as the event counts are, the chunk slots
+constexpr size_t kCapHeaderBytes = 32;
+constexpr uint32_t kCapWordUsed = 1, kCapWordDelivered = 2;
+SAME_HD inline size_t cap_spans_offset(uint32_t n_channels) { return kCapHeaderBytes + tn::events_offset(n_channels); }
+
 }  // namespace same

@@ -7,11 +7,6 @@
 
 namespace same {
 
-// where a call's chunk records lie, on the device and in the pinned copy: a header of two uint64 (captured samples of the
-// call, samples of the pool in use), the channels' chunk counts, the chunk slots
-constexpr size_t kCapHeaderBytes = 32;
-__host__ __device__ inline size_t cap_spans_offset(uint32_t n_channels) { return kCapHeaderBytes + (((size_t)n_channels * sizeof(uint32_t)) + 31) / 32 * 32; }
-
 // the device buffers of one call's capture work
 struct ToneAudioCall {
     const tn::Desc *desc;

@@ -16,24 +16,24 @@
 //                    are the same in every lane (the longest block of the 64 channels, by a butterfly of shuffles).
 //   tones_sm_kernel  lane = channel: both state machines over the call's qualify bits, events into the channel's own slots.
 // No atomics, no word passed between wavefronts.  Behind the kernels one copy of the call's counts and event slots into the
-// pinned buffer of one of kSlots slots, and an event record; a slot is reused only once its event has passed and its events
-// have been taken into the host queue.
+// pinned buffer of one of tq::kSlots slots, and an event record; a slot is reused only once its event has passed and its events
+// have been taken into the host queue.  The host half behind that wait -- where a call's records lie, the event queue, the chunk
+// logs -- is same_tone_queue.h's (host only); this file keeps the HIP resources, the slots' wait and collect, and the error text.
 // Tone-alert audio (include/same_tone_audio.h): a handle whose capture is on queues, in place of
 // tones_sm_kernel, the capture-aware state-machine kernel, the prefix kernel and the layout's copy kernel of same_tone_audio.hip,
 // and copies the call's chunk records behind its event slots.  The samples stay in the slot's pool on the device until the
-// call has passed and someone asks for them (fetch_block): same_tone_audio_peek, or the call that takes the slot next.
+// call has passed and someone asks for them (fetch_pool): same_tone_audio_peek, or the call that takes the slot next.
 // Delivery form (include/same_tone_delivery.h): a handle in delivery mode queues, behind that capture work, the
 // output-offset kernel, the decimator and the history kernel of same_tone_delivery.hip.  The float pool is then a staging buffer
-// that stays on the device; what fetch_block copies is the used part of the slot's int16 delivery pool, into a pinned host
+// that stays on the device; what fetch_pool copies is the used part of the slot's int16 delivery pool, into a pinned host
 // block that returns to a free list when its last chunk has been dropped.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <deque>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/same_tone_audio.h"
@@ -44,6 +44,7 @@
 #include "same_tone_audio_plan.h"
 #include "same_tone_delivery_kernels.h"
 #include "same_tone_delivery_plan.h"
+#include "same_tone_queue.h"
 #include "same_tones_plan.h"
 
 namespace same {
@@ -52,8 +53,6 @@ namespace {
 constexpr uint32_t kItemsPerBlock = 4;            // time-major: wavefronts of a workgroup, each on a block of its own
 constexpr uint32_t kMaxGridY = 65535;
 constexpr uint32_t kTile = 64, kTilePitch = kTile + 1;
-constexpr int kSlots = 3;
-constexpr uint64_t kMaxCallBytes = 1ull << 31;    // counts and event slots of one call
 
 template <typename SampleT>
 __global__ __launch_bounds__(64 * kItemsPerBlock) void tones_tm_kernel(const tn::Desc *__restrict__ desc, tn::Coef cf, const SampleT *__restrict__ x,
@@ -172,21 +171,8 @@ int fail(int code, const char *fmt, ...)
         if (_e != hipSuccess) return fail(SAME_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
-// a call's counts and event slots, on the device and in a slot: n_channels counts, padded to 32 bytes, then the events
-size_t events_offset(uint32_t n_channels) { return (((size_t)n_channels * sizeof(uint32_t)) + 31) / 32 * 32; }
-
 }  // namespace
 }  // namespace same
-
-// the samples of one call, on the host once fetched
-struct AudioBlock {
-    std::vector<float> data;
-    same::PinnedBuf<int16_t> pcm;                // delivery mode: the call's delivered samples, pinned; back to free_pcm behind the last drop
-    size_t chunks = 0;                           // queued chunks of the call that have not been dropped
-    uint64_t used = 0;                           // samples of the call's pool in use
-    int slot = -1;                               // the slot whose pool holds them until they are fetched; -1: fetched
-    bool published = false;                     // its chunks are in the peek view
-};
 
 struct same_tones {
     same::TonesPlan plan;
@@ -201,18 +187,15 @@ struct same_tones {
         same::PinnedBuf<uint8_t> out;
         same::Event done;
         bool in_flight = false;
-        // tone-alert audio: the call's chunk records, its sample pool, and the host block that still waits for the pool's samples
+        same::tq::Layout layout;                 // where the records of the call in this slot lie in out and cap_out
+        // tone-alert audio: the call's chunk records and its sample pool (the mode's log knows which block waits for its samples)
         same::PinnedBuf<uint8_t> cap_out;
         same::DevBuf<float> pool;
         same::DevBuf<int16_t> dpool;             // delivery mode: the call's delivery pool (pool is then the staging buffer)
-        size_t outs_offset = 0;                  // delivery mode: where the call's output records lie in cap_out
-        bool captures = false;                   // the call in this slot ran with capture on
-        AudioBlock *unfetched = nullptr;
     };
-    Slot slot[same::kSlots];
+    Slot slot[same::tq::kSlots];
     int next_slot = 0;                           // (the slots are used in turn: the oldest call in flight is in next_slot)
-    std::vector<same_tone_event> queue;          // events of the calls that have passed, from queue_head on
-    size_t queue_head = 0;
+    same::tq::EventQueue events;                 // events of the calls that have passed
     bool fed = false;                            // a call has consumed samples
 
     // tone-alert audio
@@ -222,95 +205,58 @@ struct same_tones {
     same::DevBuf<uint32_t> d_cap_flags;          // [ceil(C / 64)]
     same::DevBuf<uint8_t> d_cap_out;             // its chunk records
     hipStream_t copy_stream = nullptr;           // the lazy copies of the pools' used parts
-    std::deque<AudioBlock> blocks;               // the samples of the calls whose chunks are queued, oldest first
-    std::vector<same_tone_audio_chunk> pending;  // chunks of harvested calls (samples: the offset in the call's pool) ...
-    std::vector<same_tone_audio_chunk> ready;    // ... and, from ready_head on, the view same_tone_audio_peek hands out
-    size_t ready_head = 0;
+    // the float capture's chunks, their samples in plain host blocks that are freed behind their last drop
+    same::tq::ChunkLog<same_tone_audio_chunk, float, std::vector<float>> audio_log{0};
 
-    // delivery form: the ratio and taps, the channels' histories and capture-local clocks, and the queue in its own record
+    // delivery form: the ratio and taps, the channels' histories and capture-local clocks, and the queue in its own record:
+    // pinned host blocks, of which at most kSlots + 1 wait on the log's free list (a handle has one mode: the other log is empty)
     same::ToneDeliveryPlan delivery;
     same::DevBuf<float> d_taps_t;                // [T][L]
     same::DevBuf<float> d_hist;                  // [C][T - 1]
     same::DevBuf<uint64_t> d_anext;              // [C]
-    std::vector<same::PinnedBuf<int16_t>> free_pcm;   // host blocks whose chunks have all been dropped, at most kSlots + 1
-    std::vector<same_tone_delivery_chunk> dpending, dready;
-    size_t dready_head = 0;
+    same::tq::ChunkLog<same_tone_delivery_chunk, int16_t, same::PinnedBuf<int16_t>> delivery_log{same::tq::kSlots + 1};
 };
 
 namespace same {
 namespace {
 
-// the events of a call that has passed, by channel and inside a channel in the order its lane wrote them
+// the records of a call that has passed, into the event queue and the mode's chunk log
 void harvest(same_tones *h, same_tones::Slot &s)
 {
     const uint32_t C = h->plan.n_channels();
-    if (h->queue_head == h->queue.size()) { h->queue.clear(); h->queue_head = 0; }
-    const uint32_t *counts = (const uint32_t *)s.out.get();
-    const uint8_t *events = s.out.get() + events_offset(C);
-    for (uint32_t c = 0; c < C; ++c)
-        for (uint32_t i = 0; i < counts[c]; ++i) {
-            same_tone_event e;
-            std::memcpy(&e, events + ((size_t)s.desc[c].ev_off + i) * sizeof(same_tone_event), sizeof(e));
-            h->queue.push_back(e);
-        }
+    const tq::Records r{C, s.desc.get(), (const uint32_t *)(s.desc.get() + C), s.out.get(), s.cap_out.get(), h->delivery.params.rate};
+    h->events.harvest(s.layout, r);
     s.in_flight = false;
-    if (!s.captures) return;
-    // its chunks, by channel and inside a channel in stream order; their samples stay in the slot's pool for now
-    const uint64_t *header = (const uint64_t *)s.cap_out.get();
-    const uint32_t *n_spans = (const uint32_t *)(s.cap_out.get() + kCapHeaderBytes);
-    const uint8_t *spans = s.cap_out.get() + cap_spans_offset(C);
-    const uint32_t *span_off = (const uint32_t *)(s.desc.get() + C);
-    const bool delivery = h->delivery.on();
-    size_t n = 0;
-    for (uint32_t c = 0; c < C; ++c)
-        for (uint32_t i = 0; i < n_spans[c]; ++i, ++n) {
-            tn::Span sp;
-            std::memcpy(&sp, spans + ((size_t)span_off[c] + i) * sizeof(tn::Span), sizeof(sp));
-            if (delivery) {
-                td::Out o;
-                std::memcpy(&o, s.cap_out.get() + s.outs_offset + ((size_t)span_off[c] + i) * sizeof(td::Out), sizeof(o));
-                h->dpending.push_back(same_tone_delivery_chunk{sp.channel, sp.flags, sp.kind, h->delivery.params.rate, sp.sample_counter, o.out_index,
-                                                               o.n_out, sp.tone_start, (const int16_t *)(uintptr_t)(o.off * sizeof(int16_t))});
-                continue;
-            }
-            h->pending.push_back(same_tone_audio_chunk{sp.channel, sp.flags, sp.kind, 0, sp.sample_counter, sp.n, sp.tone_start,
-                                                       (const float *)(uintptr_t)(sp.off * sizeof(float))});
-        }
-    if (!n) return;
-    h->blocks.emplace_back();
-    AudioBlock &b = h->blocks.back();
-    b.chunks = n;
-    b.used = delivery ? header[2] : header[1];
-    if (b.used) { b.slot = (int)(&s - h->slot); s.unfetched = &b; }
+    if (!s.layout.captures()) return;
+    if (h->delivery.on()) h->delivery_log.harvest(s.layout, r, (int)(&s - h->slot));
+    else h->audio_log.harvest(s.layout, r, (int)(&s - h->slot));
 }
 
-// the used part of a passed call's pool into its host block: waits for that copy, never for a call in flight
-int fetch_block(same_tones *h, AudioBlock &b)
+// What the chunk logs fetch with: the used part of a passed call's pool into its host block -- plain memory for the float
+// capture, pinned and sized in steps of 64 Ki samples for the delivery form.  Waits for that copy, never for a call in flight.
+template <typename Block>
+int fetch_pool(same_tones *h, int slot, uint64_t used, Block &mem)
 {
-    if (b.slot < 0) return SAME_OK;
-    same_tones::Slot &s = h->slot[b.slot];
-    if (h->delivery.on()) {
-        // a free block with room, else any free block (it grows), else a new one; sizes in steps of 64 Ki samples
-        size_t pick = h->free_pcm.size();
-        for (size_t i = 0; i < h->free_pcm.size(); ++i)
-            if (h->free_pcm[i].size() >= b.used) { pick = i; break; }
-        if (pick == h->free_pcm.size() && pick) pick -= 1;
-        if (pick < h->free_pcm.size()) { b.pcm = std::move(h->free_pcm[pick]); h->free_pcm.erase(h->free_pcm.begin() + (ptrdiff_t)pick); }
-        const hipError_t e = b.pcm.ensure(((size_t)b.used + 0xffff) & ~(size_t)0xffff);
+    const void *pool;
+    if constexpr (std::is_same<Block, std::vector<float>>::value) {
+        try { mem.resize((size_t)used); } catch (...) { return fail(SAME_ENOMEM, "%llu captured samples on the host", (unsigned long long)used); }
+        pool = h->slot[slot].pool.get();
+    } else {
+        const hipError_t e = mem.ensure(((size_t)used + 0xffff) & ~(size_t)0xffff);
         if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "%llu delivered samples on the host: %s", (unsigned long long)b.used, hipGetErrorString(e));
-        TN_HIP_TRY(hipMemcpyAsync(b.pcm.get(), s.dpool.get(), (size_t)b.used * sizeof(int16_t), hipMemcpyDeviceToHost, h->copy_stream));
-        TN_HIP_TRY(hipStreamSynchronize(h->copy_stream));
-        b.slot = -1;
-        s.unfetched = nullptr;
-        return SAME_OK;
+            return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "%llu delivered samples on the host: %s", (unsigned long long)used, hipGetErrorString(e));
+        pool = h->slot[slot].dpool.get();
     }
-    try { b.data.resize((size_t)b.used); } catch (...) { return fail(SAME_ENOMEM, "%llu captured samples on the host", (unsigned long long)b.used); }
-    TN_HIP_TRY(hipMemcpyAsync(b.data.data(), s.pool.get(), (size_t)b.used * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream));
+    TN_HIP_TRY(hipMemcpyAsync(tq::block_data(mem), pool, (size_t)used * sizeof(*tq::block_data(mem)), hipMemcpyDeviceToHost, h->copy_stream));
     TN_HIP_TRY(hipStreamSynchronize(h->copy_stream));
-    b.slot = -1;
-    s.unfetched = nullptr;
     return SAME_OK;
+}
+
+// before a call writes slot's pools: the block that still waits for their samples takes them
+int fetch_slot(same_tones *h, int slot)
+{
+    const auto fetch = [h](int i, uint64_t used, auto &mem) { return fetch_pool(h, i, used, mem); };
+    return h->delivery.on() ? h->delivery_log.fetch_slot(slot, fetch) : h->audio_log.fetch_slot(slot, fetch);
 }
 
 int wait_slot(same_tones *h, same_tones::Slot &s)
@@ -324,8 +270,8 @@ int wait_slot(same_tones *h, same_tones::Slot &s)
 // the slots whose calls have passed, oldest first, up to the first that has not
 int collect(same_tones *h, bool wait)
 {
-    for (int i = 0; i < kSlots; ++i) {
-        same_tones::Slot &s = h->slot[(h->next_slot + i) % kSlots];
+    for (int i = 0; i < tq::kSlots; ++i) {
+        same_tones::Slot &s = h->slot[(h->next_slot + i) % tq::kSlots];
         if (!s.in_flight) continue;
         if (wait) { const int rc = wait_slot(h, s); if (rc) return rc; continue; }
         const hipError_t e = hipEventQuery(s.done);
@@ -334,6 +280,27 @@ int collect(same_tones *h, bool wait)
         harvest(h, s);
     }
     return SAME_OK;
+}
+
+// same_tone_audio_peek / same_tone_delivery_peek on the record's log (the log of the mode the handle is not in holds nothing)
+template <typename Log, typename Chunk>
+int peek(same_tones *h, Log same_tones::*log, const Chunk **chunks, size_t *n, const char *what)
+{
+    if (!h || !chunks || !n) return fail(SAME_EINVAL, "null argument");
+    *chunks = nullptr;
+    *n = 0;
+    TN_HIP_TRY(hipSetDevice(h->device));
+    int rc = collect(h, false), fetched = SAME_OK;
+    if (rc) return rc;
+    rc = (h->*log).publish([&](int slot, uint64_t used, auto &mem) { return fetched = fetch_pool(h, slot, used, mem); }, chunks, n);
+    return rc && !fetched ? fail(rc, "%s view", what) : rc;      // (a fetch that failed has said why)
+}
+
+template <typename Log>
+int drop(same_tones *h, Log same_tones::*log, size_t n)
+{
+    if (!h) return fail(SAME_EINVAL, "null argument");
+    return (h->*log).drop(n) ? fail(SAME_EINVAL, "more chunks than the view holds") : SAME_OK;
 }
 
 template <typename SampleT>
@@ -356,26 +323,23 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
     const TonesPlan::Shape shape = h->plan.describe(counts, n_rows, s.desc.get());
     if (!shape.any_samples) return SAME_OK;       // nothing to read: a no-op (a pending reset stays pending)
     if (!d_x) return fail(SAME_EINVAL, "null d_x with samples to read; nothing was consumed");
-    const uint64_t out_bytes = events_offset(C) + shape.event_slots * sizeof(same_tone_event);
-    if (out_bytes > kMaxCallBytes) return fail(SAME_ENOMEM, "the call needs %llu bytes of event slots; nothing was consumed", (unsigned long long)out_bytes);
+    tq::Layout at;                                // where the call's records lie, here and for its harvest
+    if (at.set_events(C, shape.event_slots)) return fail(SAME_ENOMEM, "the call needs %llu bytes of event slots; nothing was consumed", (unsigned long long)at.out_bytes);
     // (a buffer that grows is freed first, which waits for the device: nothing in flight loses it)
     hipError_t e = h->d_qual.ensure((size_t)(shape.max_complete ? shape.max_complete : 1) * C);
-    if (e == hipSuccess) e = h->d_out.ensure((size_t)out_bytes);
-    if (e == hipSuccess) e = s.out.ensure((size_t)out_bytes);
+    if (e == hipSuccess) e = h->d_out.ensure((size_t)at.out_bytes);
+    if (e == hipSuccess) e = s.out.ensure((size_t)at.out_bytes);
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the call's buffers failed: %s; nothing was consumed", hipGetErrorString(e));
     // capture on: the chunk slots behind the descriptors, room for the chunk records, and the slot's pool free to be written
     const bool capture = h->audio.on();
-    uint64_t cap_bytes = 0;
     if (capture) {
-        if (s.unfetched && (rc = fetch_block(h, *s.unfetched))) return rc;
+        if ((rc = fetch_slot(h, h->next_slot))) return rc;
         const uint64_t slots = ToneAudioPlan::describe(s.desc.get(), C, (uint32_t *)(s.desc.get() + C));
-        cap_bytes = cap_spans_offset(C) + slots * sizeof(tn::Span);
-        s.outs_offset = (size_t)cap_bytes;        // (a multiple of 16: the output records are aligned)
-        if (h->delivery.on()) cap_bytes += slots * sizeof(td::Out);
-        if (cap_bytes > kMaxCallBytes) return fail(SAME_ENOMEM, "the call needs %llu bytes of chunk slots; nothing was consumed", (unsigned long long)cap_bytes);
-        e = h->d_cap_out.ensure((size_t)cap_bytes);
-        if (e == hipSuccess) e = s.cap_out.ensure((size_t)cap_bytes);
+        if (at.set_capture(C, slots, h->delivery.on()))
+            return fail(SAME_ENOMEM, "the call needs %llu bytes of chunk slots; nothing was consumed", (unsigned long long)at.cap_bytes);
+        e = h->d_cap_out.ensure((size_t)at.cap_bytes);
+        if (e == hipSuccess) e = s.cap_out.ensure((size_t)at.cap_bytes);
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? SAME_ENOMEM : SAME_EHIP, "allocating the call's chunk records failed: %s; nothing was consumed", hipGetErrorString(e));
     }
@@ -394,7 +358,7 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
     TN_HIP_TRY(hipGetLastError());
     if (capture) {
         const ToneAudioCall k{h->d_desc.get(), (const uint32_t *)(h->d_desc.get() + C), h->d_qual.get(), h->d_sm.get(), h->d_cap.get(),
-                              h->audio.params, (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)),
+                              h->audio.params, (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + at.events_at),
                               h->d_cap_out.get(), h->d_cap_counts.get(), h->d_cap_flags.get(), s.pool.get(), h->audio.pool_cap,
                               h->plan.coef.N, C};
         TN_HIP_TRY(tone_audio_launch_sm(k, stream));
@@ -403,23 +367,23 @@ int process(same_tones *h, const SampleT *d_x, size_t n_rows, const uint32_t *co
             const td::Params &p = h->delivery.params;
             // a chunk has at most n_rows placed rows: its outputs, in tiles of 256
             const uint64_t most = rs::outputs_after(n_rows, p.L, p.M) + 1;
-            const ToneDeliveryCall dk{p, h->d_taps_t.get(), h->d_hist.get(), h->d_anext.get(), s.dpool.get(), s.outs_offset,
+            const ToneDeliveryCall dk{p, h->d_taps_t.get(), h->d_hist.get(), h->d_anext.get(), s.dpool.get(), at.outs_at,
                                       (uint32_t)((most + td::kTileOutputs - 1) / td::kTileOutputs)};
             TN_HIP_TRY(tone_delivery_launch(k, dk, stream));
             TN_HIP_TRY(tone_delivery_launch_history(k, dk, d_x, n_rows, layout, stream));
         }
-        TN_HIP_TRY(hipMemcpyAsync(s.cap_out.get(), h->d_cap_out.get(), (size_t)cap_bytes, hipMemcpyDeviceToHost, stream));
+        TN_HIP_TRY(hipMemcpyAsync(s.cap_out.get(), h->d_cap_out.get(), (size_t)at.cap_bytes, hipMemcpyDeviceToHost, stream));
     } else {
         hipLaunchKernelGGL(tones_sm_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, h->d_desc.get(), h->plan.coef.N, h->d_qual.get(),
-                           h->d_sm.get(), (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + events_offset(C)), C);
+                           h->d_sm.get(), (uint32_t *)h->d_out.get(), (same_tone_event *)(h->d_out.get() + at.events_at), C);
         TN_HIP_TRY(hipGetLastError());
     }
-    TN_HIP_TRY(hipMemcpyAsync(s.out.get(), h->d_out.get(), (size_t)out_bytes, hipMemcpyDeviceToHost, stream));
+    TN_HIP_TRY(hipMemcpyAsync(s.out.get(), h->d_out.get(), (size_t)at.out_bytes, hipMemcpyDeviceToHost, stream));
     TN_HIP_TRY(hipEventRecord(s.done, stream));
     s.in_flight = true;
-    s.captures = capture;
+    s.layout = at;
     h->fed = true;
-    h->next_slot = (h->next_slot + 1) % kSlots;
+    h->next_slot = (h->next_slot + 1) % tq::kSlots;
     h->plan.commit(s.desc.get());
     return SAME_OK;
 }
@@ -517,51 +481,8 @@ int same_tone_audio_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, uin
     return SAME_OK;
 }
 
-int same_tone_audio_peek(same_tones *h, const same_tone_audio_chunk **chunks, size_t *n)
-{
-    if (!h || !chunks || !n) return fail(SAME_EINVAL, "null argument");
-    *chunks = nullptr;
-    *n = 0;
-    TN_HIP_TRY(hipSetDevice(h->device));
-    int rc = collect(h, false);
-    if (rc) return rc;
-    if (h->delivery.on()) return SAME_OK;         // (its chunks are same_tone_delivery_peek's)
-    if (h->ready_head == h->ready.size()) { h->ready.clear(); h->ready_head = 0; }
-    // the harvested calls' samples come to the host, and their chunks into the view
-    size_t at = 0;
-    for (AudioBlock &b : h->blocks) {
-        if (b.published) continue;
-        if ((rc = fetch_block(h, b))) break;
-        try { h->ready.reserve(h->ready.size() + b.chunks); } catch (...) { rc = fail(SAME_ENOMEM, "audio view"); break; }
-        for (size_t i = 0; i < b.chunks; ++i) {
-            same_tone_audio_chunk ch = h->pending[at + i];
-            ch.samples = ch.n_samples ? b.data.data() + (uintptr_t)ch.samples / sizeof(float) : nullptr;
-            h->ready.push_back(ch);
-        }
-        at += b.chunks;
-        b.published = true;
-    }
-    h->pending.erase(h->pending.begin(), h->pending.begin() + (ptrdiff_t)at);
-    if (rc) return rc;
-    *n = h->ready.size() - h->ready_head;
-    *chunks = *n ? h->ready.data() + h->ready_head : nullptr;
-    return SAME_OK;
-}
-
-int same_tone_audio_drop(same_tones *h, size_t n)
-{
-    if (!h) return fail(SAME_EINVAL, "null argument");
-    if (n > h->ready.size() - h->ready_head) return fail(SAME_EINVAL, "more chunks than the view holds");
-    h->ready_head += n;
-    while (n) {                                   // (the view's chunks are those of the oldest blocks)
-        AudioBlock &b = h->blocks.front();
-        const size_t k = n < b.chunks ? n : b.chunks;
-        b.chunks -= k;
-        n -= k;
-        if (b.chunks == 0) h->blocks.pop_front();
-    }
-    return SAME_OK;
-}
+int same_tone_audio_peek(same_tones *h, const same_tone_audio_chunk **chunks, size_t *n) { return peek(h, &same_tones::audio_log, chunks, n, "audio"); }
+int same_tone_audio_drop(same_tones *h, size_t n) { return drop(h, &same_tones::audio_log, n); }
 
 int same_tone_delivery_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, uint32_t max_blocks, size_t samples_per_call, uint32_t out_rate,
                            float gain)
@@ -598,56 +519,8 @@ int same_tone_delivery_set(same_tones *h, uint32_t kinds, uint32_t tail_blocks, 
     return SAME_OK;
 }
 
-int same_tone_delivery_peek(same_tones *h, const same_tone_delivery_chunk **chunks, size_t *n)
-{
-    if (!h || !chunks || !n) return fail(SAME_EINVAL, "null argument");
-    *chunks = nullptr;
-    *n = 0;
-    TN_HIP_TRY(hipSetDevice(h->device));
-    int rc = collect(h, false);
-    if (rc) return rc;
-    if (!h->delivery.on()) return SAME_OK;
-    if (h->dready_head == h->dready.size()) { h->dready.clear(); h->dready_head = 0; }
-    // the harvested calls' samples come to the host, and their chunks into the view
-    size_t at = 0;
-    for (AudioBlock &b : h->blocks) {
-        if (b.published) continue;
-        if ((rc = fetch_block(h, b))) break;
-        try { h->dready.reserve(h->dready.size() + b.chunks); } catch (...) { rc = fail(SAME_ENOMEM, "delivery view"); break; }
-        for (size_t i = 0; i < b.chunks; ++i) {
-            same_tone_delivery_chunk ch = h->dpending[at + i];
-            ch.samples = ch.n_samples ? b.pcm.get() + (uintptr_t)ch.samples / sizeof(int16_t) : nullptr;
-            h->dready.push_back(ch);
-        }
-        at += b.chunks;
-        b.published = true;
-    }
-    h->dpending.erase(h->dpending.begin(), h->dpending.begin() + (ptrdiff_t)at);
-    if (rc) return rc;
-    *n = h->dready.size() - h->dready_head;
-    *chunks = *n ? h->dready.data() + h->dready_head : nullptr;
-    return SAME_OK;
-}
-
-int same_tone_delivery_drop(same_tones *h, size_t n)
-{
-    if (!h) return fail(SAME_EINVAL, "null argument");
-    if (n > h->dready.size() - h->dready_head) return fail(SAME_EINVAL, "more chunks than the view holds");
-    h->dready_head += n;
-    while (n) {                                   // (the view's chunks are those of the oldest blocks)
-        AudioBlock &b = h->blocks.front();
-        const size_t k = n < b.chunks ? n : b.chunks;
-        b.chunks -= k;
-        n -= k;
-        if (b.chunks) continue;
-        // the block's memory is recycled: pinning it again for every call would cost more than the copy
-        if (b.pcm.get() && h->free_pcm.size() <= (size_t)kSlots) {
-            try { h->free_pcm.push_back(std::move(b.pcm)); } catch (...) { }
-        }
-        h->blocks.pop_front();
-    }
-    return SAME_OK;
-}
+int same_tone_delivery_peek(same_tones *h, const same_tone_delivery_chunk **chunks, size_t *n) { return peek(h, &same_tones::delivery_log, chunks, n, "delivery"); }
+int same_tone_delivery_drop(same_tones *h, size_t n) { return drop(h, &same_tones::delivery_log, n); }
 
 uint32_t same_tone_audio_chunk_bound(uint32_t n_blocks) { return tn::chunk_bound(n_blocks); }
 
@@ -696,12 +569,7 @@ int same_tones_poll(same_tones *h, same_tone_event *out, size_t cap, size_t *n_o
     TN_HIP_TRY(hipSetDevice(h->device));
     const int rc = collect(h, false);
     if (rc) return rc;
-    size_t have = h->queue.size() - h->queue_head;
-    const size_t n = have < cap ? have : cap;
-    if (n) std::memcpy(out, h->queue.data() + h->queue_head, n * sizeof(same_tone_event));
-    h->queue_head += n;
-    *n_out = n;
-    if (n_left) *n_left = have - n;
+    *n_out = h->events.take(out, cap, n_left);
     return SAME_OK;
 }
 

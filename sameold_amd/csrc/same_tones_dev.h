@@ -124,6 +124,9 @@ SAME_HD inline uint32_t sm_step(Sm &s, bool q, uint64_t b, uint32_t N, uint32_t 
 // (tests/helpers/tones_main.cpp runs it).  The two classes are independent: twice that.
 SAME_HD inline uint32_t events_bound(uint32_t n) { return SAME_TONES_EVENTS_BOUND(n); }
 
+// a call's counts and event slots, on the device and in a slot's pinned copy: n_channels counts, padded to 32 bytes, then the events
+SAME_HD inline size_t events_offset(uint32_t n_channels) { return (((size_t)n_channels * sizeof(uint32_t)) + 31) / 32 * 32; }
+
 // a channel's part of one call (same_tones_plan.h fills it)
 struct Desc {
     uint64_t block0;          // index of the first block the call touches, counted from the channel's start or last reset

@@ -230,23 +230,27 @@ class ToneDetector:
         capture off."""
         _check(self._L.same_tone_audio_set(self._h, int(kinds), int(tail_blocks), int(max_blocks), int(samples_per_call)))
 
+    def _take(self, peek, drop, dtype: np.dtype, sample) -> list:
+        """The view `peek` hands out as (record, owned samples) pairs, dropped with `drop`; `sample`: the ctypes type of a sample"""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        _check(peek(self._h, C.byref(ptr), C.byref(n)))
+        out = []
+        if n.value:
+            raw = (C.c_char * (n.value * dtype.itemsize)).from_address(ptr.value)
+            recs = np.frombuffer(raw, dtype=dtype).copy()
+            for r in recs:
+                k = int(r["n_samples"])
+                a = np.ctypeslib.as_array(C.cast(int(r["samples"]), C.POINTER(sample)), shape=(k,)).copy() if k else np.zeros(0, sample)
+                r["samples"] = 0
+                out.append((r, a))
+            _check(drop(self._h, n.value))
+        return out
+
     def poll_audio(self) -> list:
         """The queued audio chunks of the calls that have passed, which are then dropped: (record, samples) pairs, the record a
         TONE_AUDIO_CHUNK_DTYPE scalar (its `samples` field is 0) and the samples an owned float32 array.  Calls in call order;
         inside a call by channel, then by sample_counter.  `sync()` first to include the calls in flight."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        _check(self._L.same_tone_audio_peek(self._h, C.byref(ptr), C.byref(n)))
-        out = []
-        if n.value:
-            raw = (C.c_char * (n.value * TONE_AUDIO_CHUNK_DTYPE.itemsize)).from_address(ptr.value)
-            recs = np.frombuffer(raw, dtype=TONE_AUDIO_CHUNK_DTYPE).copy()
-            for r in recs:
-                k = int(r["n_samples"])
-                a = np.ctypeslib.as_array(C.cast(int(r["samples"]), C.POINTER(C.c_float)), shape=(k,)).copy() if k else np.zeros(0, np.float32)
-                r["samples"] = 0
-                out.append((r, a))
-            _check(self._L.same_tone_audio_drop(self._h, n.value))
-        return out
+        return self._take(self._L.same_tone_audio_peek, self._L.same_tone_audio_drop, TONE_AUDIO_CHUNK_DTYPE, C.c_float)
 
     def set_audio_delivery(self, kinds: int, tail_blocks: int, max_blocks: int, samples_per_call: int, out_rate: int, gain: float = 1.0) -> None:
         """Tone alert in delivery form (same_tone_delivery_set), in place of `set_audio_capture` and under its rules: the same
@@ -260,19 +264,7 @@ class ToneDetector:
         """The queued delivery chunks of the calls that have passed, which are then dropped: (record, samples) pairs, the record a
         TONE_DELIVERY_CHUNK_DTYPE scalar (its `samples` field is 0) and the samples an owned int16 array.  The order is
         `poll_audio`'s.  `sync()` first to include the calls in flight.  Empty on a detector that is not in delivery form."""
-        ptr, n = C.c_void_p(), C.c_size_t()
-        _check(self._L.same_tone_delivery_peek(self._h, C.byref(ptr), C.byref(n)))
-        out = []
-        if n.value:
-            raw = (C.c_char * (n.value * TONE_DELIVERY_CHUNK_DTYPE.itemsize)).from_address(ptr.value)
-            recs = np.frombuffer(raw, dtype=TONE_DELIVERY_CHUNK_DTYPE).copy()
-            for r in recs:
-                k = int(r["n_samples"])
-                a = np.ctypeslib.as_array(C.cast(int(r["samples"]), C.POINTER(C.c_int16)), shape=(k,)).copy() if k else np.zeros(0, np.int16)
-                r["samples"] = 0
-                out.append((r, a))
-            _check(self._L.same_tone_delivery_drop(self._h, n.value))
-        return out
+        return self._take(self._L.same_tone_delivery_peek, self._L.same_tone_delivery_drop, TONE_DELIVERY_CHUNK_DTYPE, C.c_int16)
 
     def reset_channels(self, channels) -> None:
         """The listed channels start again at this point of the stream (same_tones_reset_channels).  An active tone emits no

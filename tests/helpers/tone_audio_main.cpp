@@ -2,9 +2,11 @@
 // (same_tone_audio_dev.h, same_tones_dev.h), for tests/test_tone_audio_cpu.py under ASan + UBSan.  It runs calls the way
 // same_tones.hip and same_tone_audio.hip do -- describe, the chunk slots, every (channel, block) item, run_capture per channel
 // over the call's qualify bits, an exclusive prefix over the channels' captured counts, span_place, a plain C++ copy out of the
-// call's buffer into the call's pool, the harvest by channel -- on buffers of exactly the size the library provides: the input
-// with NaN (f32) or 32767 (int16) behind every channel's count, chunk slots of exactly the plan's number, a pool of exactly
-// samples_per_call floats.  Layouts alternate from call to call.
+// call's buffer into the call's pool -- on buffers of exactly the size the library provides: the input with NaN (f32) or 32767
+// (int16) behind every channel's count, the two record buffers of exactly the layout's bytes (same_tone_queue.h), a pool of
+// exactly samples_per_call floats.  Behind a call comes the library's own harvest: the unit's event queue and chunk log take the
+// call's records, the log fetches the pool's used part with a memcpy, and what is printed is what the queue and the published
+// view hold.  Layouts alternate from call to call.
 //
 //     tone_audio_main streams IN_FILE f32|i16 RATE CHANNELS CUT KINDS TAIL_BLOCKS MAX_BLOCKS POOL RESET_CHANNEL RESET_AFTER OUT_FILE
 //         IN_FILE: [CHANNELS x samples] channel-major, little-endian f32 or int16.  CUT: "fixed" -- plain calls of 1, 319, 320,
@@ -17,6 +19,7 @@
 //         stdout: "bound N CHUNKS LIMIT" for N = 0 .. 200: the chunks of a channel that completes N blocks on the adversarial
 //         pattern of same_tone_audio_dev.h, and chunk_bound(N); "OK".
 #include "../../sameold_amd/csrc/same_tone_audio_plan.h"
+#include "../../sameold_amd/csrc/same_tone_queue.h"
 #include "../../sameold_amd/csrc/same_tones_plan.h"
 
 #include <cstdio>
@@ -33,6 +36,7 @@
     } while (0)
 
 namespace tn = same::tn;
+namespace tq = same::tq;
 using same::ToneAudioPlan;
 using same::TonesPlan;
 
@@ -61,6 +65,8 @@ struct Runner {
     std::vector<float> acc;
     std::vector<tn::Sm> sm;
     std::vector<tn::Cap> cap;
+    tq::EventQueue events;
+    tq::ChunkLog<same_tone_audio_chunk, float, std::vector<float>> log{0};
     std::vector<float> captured;                         // every queued chunk's samples, in queue order
     uint32_t calls = 0;
 
@@ -93,8 +99,12 @@ struct Runner {
         for (uint32_t c = 0; c < C; ++c) std::printf(" %u", desc[c].count);
         std::printf("\n");
         std::vector<uint8_t> qual((size_t)(shape.max_complete ? shape.max_complete : 1) * C, 0xff);
-        std::vector<same_tone_event> ev((size_t)shape.event_slots);
-        std::vector<tn::Span> spans((size_t)slots);
+        // the call's two record buffers, as the device writes them
+        tq::Layout at;
+        CHECK(at.set_events(C, shape.event_slots) == SAME_OK && at.set_capture(C, slots, false) == SAME_OK);
+        std::vector<uint8_t> out((size_t)at.out_bytes, 0xee), cap_out((size_t)at.cap_bytes, 0xee);
+        same_tone_event *ev = (same_tone_event *)(out.data() + at.events_at);
+        tn::Span *spans = (tn::Span *)(cap_out.data() + at.spans_at);
         const size_t bank_words = (size_t)tn::kAccWords * C;
         for (uint32_t c = 0; c < C; ++c) {
             const tn::Desc &d = desc[c];
@@ -113,9 +123,9 @@ struct Runner {
         std::vector<uint32_t> n_ev(C, 0), n_spans(C, 0);
         std::vector<uint64_t> count(C, 0);
         for (uint32_t c = 0; c < C; ++c) {
-            // (spans.data() + offset, not &spans[offset]: a channel with no slot may sit at the end)
-            count[c] = tn::run_capture(desc[c], N, c, C, qual.data(), &sm[2 * (size_t)c], cap[c], audio.params, ev.data(), &n_ev[c],
-                                       spans.data() + span_off[c], &n_spans[c]);
+            // (spans + offset, not &spans[offset]: a channel with no slot may sit at the end)
+            count[c] = tn::run_capture(desc[c], N, c, C, qual.data(), &sm[2 * (size_t)c], cap[c], audio.params, ev, &n_ev[c],
+                                       spans + span_off[c], &n_spans[c]);
             CHECK(n_ev[c] <= tn::events_bound(desc[c].n_complete) && n_spans[c] <= tn::chunk_bound(desc[c].n_complete));
             uint64_t sum = 0;
             for (uint32_t i = 0; i < n_spans[c]; ++i) {
@@ -133,6 +143,10 @@ struct Runner {
             base += count[c];
         }
         const uint64_t used = base < audio.pool_cap ? base : audio.pool_cap;
+        const uint64_t header[2] = {base, used};
+        std::memcpy(cap_out.data(), header, sizeof(header));
+        std::memcpy(out.data(), n_ev.data(), (size_t)C * sizeof(uint32_t));
+        std::memcpy(cap_out.data() + same::kCapHeaderBytes, n_spans.data(), (size_t)C * sizeof(uint32_t));
         // the copy kernel, into a pool of exactly the capacity
         std::vector<float> pool((size_t)audio.pool_cap, -12345.5f);
         for (uint32_t c = 0; c < C; ++c)
@@ -143,25 +157,41 @@ struct Runner {
                     pool[(size_t)(s.off + t)] = (float)(layout == SAME_LAYOUT_TIME_MAJOR ? x[row * C + c] : x[(size_t)c * n_rows + row]);
                 }
             }
-        // the harvest: events and chunks by channel
-        for (uint32_t c = 0; c < C; ++c)
-            for (uint32_t i = 0; i < n_ev[c]; ++i) {
-                const same_tone_event &e = ev[desc[c].ev_off + i];
-                std::printf("event %u %u %u %u %llu %llu\n", calls, c, e.kind, e.edge, (unsigned long long)e.sample_counter,
-                            (unsigned long long)e.duration);
-            }
+        // the pool is filled without a gap
         uint64_t seen = 0;
         for (uint32_t c = 0; c < C; ++c)
             for (uint32_t i = 0; i < n_spans[c]; ++i) {
                 const tn::Span &s = spans[span_off[c] + i];
-                CHECK(s.n == 0 || s.off == seen);            // the pool is filled without a gap
-                CHECK(s.n == 0 || s.off + s.n <= used);
+                CHECK(s.n == 0 || (s.off == seen && s.off + s.n <= used));
                 seen += s.n;
-                std::printf("chunk %u %u %u %u %llu %llu %llu %zu\n", calls, c, s.flags, s.kind, (unsigned long long)s.sample_counter,
-                            (unsigned long long)s.n, (unsigned long long)s.tone_start, captured.size());
-                captured.insert(captured.end(), pool.begin() + (ptrdiff_t)s.off, pool.begin() + (ptrdiff_t)(s.off + s.n));
             }
         CHECK(seen == used);
+        // the harvest: the unit's, into the slot the library would use; then what the queue and the view hold, and all of it leaves
+        const tq::Records r{C, desc.data(), span_off.data(), out.data(), cap_out.data(), 0};
+        events.harvest(at, r);
+        log.harvest(at, r, (int)(calls % tq::kSlots));
+        std::vector<same_tone_event> got(events.queue.size() - events.head);
+        size_t left = 1;
+        CHECK(events.take(got.data(), got.size(), &left) == got.size() && left == 0);
+        for (const same_tone_event &e : got)
+            std::printf("event %u %u %u %u %llu %llu\n", calls, e.channel, e.kind, e.edge, (unsigned long long)e.sample_counter,
+                        (unsigned long long)e.duration);
+        const same_tone_audio_chunk *view = nullptr;
+        size_t n_view = 0;
+        const auto fetch = [&](int, uint64_t n, std::vector<float> &mem) {
+            mem.resize((size_t)n);
+            std::memcpy(mem.data(), pool.data(), (size_t)n * sizeof(float));
+            return (int)SAME_OK;
+        };
+        CHECK(log.publish(fetch, &view, &n_view) == SAME_OK);
+        for (size_t i = 0; i < n_view; ++i) {
+            const same_tone_audio_chunk &ch = view[i];
+            CHECK(ch.reserved == 0 && (ch.samples != nullptr) == (ch.n_samples != 0));
+            std::printf("chunk %u %u %u %u %llu %llu %llu %zu\n", calls, ch.channel, ch.flags, ch.kind, (unsigned long long)ch.sample_counter,
+                        (unsigned long long)ch.n_samples, (unsigned long long)ch.tone_start, captured.size());
+            captured.insert(captured.end(), ch.samples, ch.samples + ch.n_samples);
+        }
+        CHECK(log.drop(n_view + 1) == SAME_EINVAL && log.drop(n_view) == SAME_OK);
         plan.commit(desc.data());
         ++calls;
     }

@@ -5,8 +5,11 @@
 // chunk's outputs (td::out_of) with an exclusive prefix over the channels' delivered counts, every tile of 256 outputs from a
 // window of exactly the tile's length (td::tile_of, window_at, tile_output), and td::history_step per channel on the call's input
 // -- on buffers of exactly the size the library provides: the input with NaN (f32) or 32767 (int16) behind every channel's
-// count, a staging pool of samples_per_call floats, a delivery pool of samples_per_call int16, T - 1 history floats per channel
-// that start as NaN.  Layouts alternate from call to call.
+// count, the two record buffers of exactly the layout's bytes (same_tone_queue.h), a staging pool of samples_per_call floats, a
+// delivery pool of samples_per_call int16, T - 1 history floats per channel that start as NaN.  Behind a call comes the library's
+// own harvest: the unit's chunk log takes the call's records and fetches the delivery pool's used part with a memcpy, and what
+// is printed is what the published view holds (ROWS, which the public record does not carry, from the call's chunk slots in the
+// view's order).  Layouts alternate from call to call.
 //
 //     tone_delivery_main IN_FILE f32|i16 RATE CHANNELS CUT KINDS TAIL_BLOCKS MAX_BLOCKS POOL RESET_CHANNEL RESET_AFTER OUT_RATE GAIN OUT_FILE
 //         IN_FILE: [CHANNELS x samples] channel-major, little-endian f32 or int16.  CUT: "fixed" -- plain calls of 1, 319, 320,
@@ -17,6 +20,7 @@
 //         COUNTER ROWS TONE_START OUT_INDEX N_SAMPLES AT" in queue order (ROWS: the placed rows; AT: the first sample's index in
 //         OUT_FILE, int16), "OK".
 #include "../../sameold_amd/csrc/same_tone_delivery_plan.h"
+#include "../../sameold_amd/csrc/same_tone_queue.h"
 #include "../../sameold_amd/csrc/same_tones_plan.h"
 
 #include <cstdio>
@@ -34,6 +38,7 @@
 
 namespace tn = same::tn;
 namespace td = same::td;
+namespace tq = same::tq;
 using same::ToneAudioPlan;
 using same::ToneDeliveryPlan;
 using same::TonesPlan;
@@ -65,6 +70,7 @@ struct Runner {
     std::vector<tn::Cap> cap;
     std::vector<float> hist;                             // [C][T - 1]
     std::vector<uint64_t> a_next;                        // [C]
+    tq::ChunkLog<same_tone_delivery_chunk, int16_t, std::vector<int16_t>> log{tq::kSlots + 1};
     std::vector<int16_t> delivered;                      // every queued chunk's samples, in queue order
     uint32_t calls = 0;
 
@@ -109,8 +115,13 @@ struct Runner {
         for (uint32_t c = 0; c < C; ++c) std::printf(" %u", desc[c].count);
         std::printf("\n");
         std::vector<uint8_t> qual((size_t)(shape.max_complete ? shape.max_complete : 1) * C, 0xff);
-        std::vector<same_tone_event> ev((size_t)shape.event_slots);
-        std::vector<tn::Span> spans((size_t)slots);
+        // the call's two record buffers, as the device writes them
+        tq::Layout at;
+        CHECK(at.set_events(C, shape.event_slots) == SAME_OK && at.set_capture(C, slots, true) == SAME_OK);
+        std::vector<uint8_t> out((size_t)at.out_bytes, 0xee), cap_out((size_t)at.cap_bytes, 0xee);
+        same_tone_event *ev = (same_tone_event *)(out.data() + at.events_at);
+        tn::Span *spans = (tn::Span *)(cap_out.data() + at.spans_at);
+        td::Out *outs = (td::Out *)(cap_out.data() + at.outs_at);
         const size_t bank_words = (size_t)tn::kAccWords * C;
         for (uint32_t c = 0; c < C; ++c) {
             const tn::Desc &d = desc[c];
@@ -130,8 +141,8 @@ struct Runner {
         std::vector<uint64_t> count(C, 0), entry_first(C, 0);
         for (uint32_t c = 0; c < C; ++c) entry_first[c] = cap[c].first;
         for (uint32_t c = 0; c < C; ++c)
-            count[c] = tn::run_capture(desc[c], N, c, C, qual.data(), &sm[2 * (size_t)c], cap[c], audio.params, ev.data(), &n_ev[c],
-                                       spans.data() + span_off[c], &n_spans[c]);
+            count[c] = tn::run_capture(desc[c], N, c, C, qual.data(), &sm[2 * (size_t)c], cap[c], audio.params, ev, &n_ev[c],
+                                       spans + span_off[c], &n_spans[c]);
         uint64_t base = 0;
         for (uint32_t c = 0; c < C; ++c) {
             for (uint32_t i = 0; i < n_spans[c]; ++i) tn::span_place(spans[span_off[c] + i], base, audio.pool_cap);
@@ -147,8 +158,8 @@ struct Runner {
                 }
             }
         // the output-offset kernel: every chunk's outputs, then the delivery pool in chunk order
-        std::vector<td::Out> outs((size_t)slots);
         uint64_t used = 0;
+        std::vector<uint64_t> rows;                          // the chunks' placed rows, by channel
         for (uint32_t c = 0; c < C; ++c) {
             uint64_t v = 0;
             for (uint32_t i = 0; i < n_spans[c]; ++i) {
@@ -159,6 +170,7 @@ struct Runner {
                 CHECK((s.flags & SAME_TONE_AUDIO_FIRST) ? o.a == 0 : o.a == s.sample_counter - entry_first[c]);     // the capture's own clock
                 CHECK(o.n_out <= s.n);                                             // L <= M: never more outputs than placed rows
                 v += o.n_out;
+                rows.push_back(s.n);
             }
             for (uint32_t i = 0; i < n_spans[c]; ++i) outs[span_off[c] + i].off += used;
             used += v;
@@ -185,20 +197,38 @@ struct Runner {
             td::history_step(desc[c], cap[c], N, p.T, xc, layout == SAME_LAYOUT_TIME_MAJOR ? (size_t)C : (size_t)1,
                              hist.data() + (size_t)c * (p.T - 1), 1, &a_next[c]);
         }
-        // the harvest: chunks by channel
+        // the delivery pool is filled without a gap and without padding
         uint64_t seen = 0;
         for (uint32_t c = 0; c < C; ++c)
             for (uint32_t i = 0; i < n_spans[c]; ++i) {
-                const tn::Span &s = spans[span_off[c] + i];
-                const td::Out &o = outs[span_off[c] + i];
-                CHECK(o.off == seen);                        // the delivery pool is filled without a gap and without padding
-                seen += o.n_out;
-                std::printf("chunk %u %u %u %u %llu %llu %llu %llu %llu %zu\n", calls, c, s.flags, s.kind, (unsigned long long)s.sample_counter,
-                            (unsigned long long)s.n, (unsigned long long)s.tone_start, (unsigned long long)o.out_index, (unsigned long long)o.n_out,
-                            delivered.size());
-                delivered.insert(delivered.end(), dpool.begin() + (ptrdiff_t)o.off, dpool.begin() + (ptrdiff_t)(o.off + o.n_out));
+                CHECK(outs[span_off[c] + i].off == seen);
+                seen += outs[span_off[c] + i].n_out;
             }
         CHECK(seen == used);
+        // the harvest: the unit's, into the slot the library would use; then what the view holds, and all of it leaves
+        const uint64_t header[3] = {base, base < audio.pool_cap ? base : audio.pool_cap, used};
+        std::memcpy(cap_out.data(), header, sizeof(header));
+        std::memcpy(out.data(), n_ev.data(), (size_t)C * sizeof(uint32_t));
+        std::memcpy(cap_out.data() + same::kCapHeaderBytes, n_spans.data(), (size_t)C * sizeof(uint32_t));
+        const tq::Records r{C, desc.data(), span_off.data(), out.data(), cap_out.data(), p.rate};
+        log.harvest(at, r, (int)(calls % tq::kSlots));         // (this driver prints no events: tone_audio_main.cpp harvests them)
+        const same_tone_delivery_chunk *view = nullptr;
+        size_t n_view = 0;
+        const auto fetch = [&](int, uint64_t n, std::vector<int16_t> &mem) {
+            if (mem.size() < n) mem.resize((size_t)n);
+            std::memcpy(mem.data(), dpool.data(), (size_t)n * sizeof(int16_t));
+            return (int)SAME_OK;
+        };
+        CHECK(log.publish(fetch, &view, &n_view) == SAME_OK && n_view == rows.size());
+        for (size_t i = 0; i < n_view; ++i) {
+            const same_tone_delivery_chunk &ch = view[i];
+            CHECK(ch.rate == p.rate && (ch.samples != nullptr) == (ch.n_samples != 0));
+            std::printf("chunk %u %u %u %u %llu %llu %llu %llu %llu %zu\n", calls, ch.channel, ch.flags, ch.kind, (unsigned long long)ch.sample_counter,
+                        (unsigned long long)rows[i], (unsigned long long)ch.tone_start, (unsigned long long)ch.out_index,
+                        (unsigned long long)ch.n_samples, delivered.size());
+            delivered.insert(delivered.end(), ch.samples, ch.samples + ch.n_samples);
+        }
+        CHECK(log.drop(n_view + 1) == SAME_EINVAL && log.drop(n_view) == SAME_OK && log.n_free() <= (size_t)tq::kSlots + 1);
         plan.commit(desc.data());
         ++calls;
     }

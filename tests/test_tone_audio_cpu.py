@@ -1,7 +1,7 @@
 """Tone-alert audio's host plan (sameold_amd/csrc/same_tone_audio_plan.h) and device core (same_tone_audio_dev.h: the text the
 device runs) compiled with plain g++ under ASan + UBSan, driven by tests/helpers/tone_audio_main.cpp the way same_tones.hip and
-same_tone_audio.hip drive them, and held against the numpy reference (tests/helpers/tone_audio_reference.py): every chunk's
-samples bit for bit, flags, counters and the queue order, three cuts of the same streams, a pool that fills, a reset in
+same_tone_audio.hip drive them -- the harvest, the published view and the drop are the library's own (same_tone_queue.h) --
+and held against the numpy reference (tests/helpers/tone_audio_reference.py): every chunk's samples bit for bit, flags, counters and the queue order, three cuts of the same streams, a pool that fills, a reset in
 mid-capture, a tail that bridges two tones, the chunk bound on its adversarial pattern.  Every test first holds the reference
 alone to the captures the streams were made for."""
 import os

@@ -1,8 +1,9 @@
 """Tone-alert audio on the device (include/same_tone_audio.h, sameold_amd/csrc/same_tone_audio.hip) against the numpy
 restatement of its contract (tests/helpers/tone_audio_reference.py): every chunk bit for bit with its flags, counters and
 queue order, over 130 channels (two whole groups of 64 and a partial one), both layouts, f32 and int16, plain and ragged calls;
-a group in which nobody captures between two that do; a pool that fills; a handle with capture off.  The tone events beside a
-capture are those of a handle without one."""
+a group in which nobody captures between two that do; a pool that fills; a handle with capture off; calls that nobody syncs or
+polls between, so that a slot is taken again with its samples still on the device, with one poll behind them and with a view
+dropped in parts through the raw peek and drop.  The tone events beside a capture are those of a handle without one."""
 import os
 import sys
 
@@ -194,3 +195,76 @@ def test_refusals_and_the_view(sa):
     assert e.value.code == -1
     td.sync()
     assert td.poll_audio() == [] and len(td.poll()) == 0
+
+
+def run_unpolled(sa, x, rate, calls, dtype, layout, setup):
+    """the ragged calls through a ToneDetector that `setup` has put into its mode, with no sync and no poll between them, then
+    one sync: a slot is taken again while the samples of the call before are still on the device"""
+    td = sa.ToneDetector(x.shape[0], rate)
+    setup(td)
+    done = np.zeros(x.shape[0], np.int64)
+    for k in calls:
+        td.process(device_input(x, done, k, dtype, layout), k, layout)
+        done += k
+    td.sync()
+    return td
+
+
+def raw_view(td, peek, rec_dtype, fields, sample):
+    """the view of a raw same_tone_*_peek, as the reference lists chunks: the `fields` of each record, then its samples read through
+    the record's pointer"""
+    import ctypes
+    ptr, n = ctypes.c_void_p(), ctypes.c_size_t()
+    assert peek(td._h, ctypes.byref(ptr), ctypes.byref(n)) == 0
+    if not n.value:
+        return []
+    recs = np.frombuffer((ctypes.c_char * (n.value * rec_dtype.itemsize)).from_address(ptr.value), dtype=rec_dtype)
+    out = []
+    for r in recs:
+        k = int(r["n_samples"])
+        assert (int(r["samples"]) != 0) == (k != 0)
+        a = np.ctypeslib.as_array(ctypes.cast(int(r["samples"]), ctypes.POINTER(sample)), shape=(k,)).copy() if k else np.zeros(0, sample)
+        out.append(tuple(int(r[f]) for f in fields) + (a,))
+    return out
+
+
+def assert_view_dropped_in_parts(td, peek, drop, rec_dtype, fields, sample, flat, same):
+    """drop 1, peek, drop half of the rest, peek, drop all: after each peek the view is the matching tail of `flat`"""
+    view = lambda: raw_view(td, peek, rec_dtype, fields, sample)  # noqa: E731
+    n = len(flat)
+    assert n > 6
+    same([view()], [flat], "the whole view")
+    assert drop(td._h, n + 1) < 0                            # more than the view holds: refused, nothing changes
+    assert drop(td._h, 1) == 0
+    same([view()], [flat[1:]], "behind drop(1)")
+    half = (n - 1) // 2
+    assert 0 < half < n - 1 and drop(td._h, half) == 0
+    same([view()], [flat[1 + half:]], "behind half of the rest")
+    assert drop(td._h, n - 1 - half) == 0
+    assert view() == [] and drop(td._h, 0) == 0 and drop(td._h, 1) < 0
+
+
+AUDIO_FIELDS = ("channel", "flags", "kind", "sample_counter", "tone_start")
+
+
+def unpolled_audio(sa):
+    x, calls, want = case(8000, "skip", True)
+    # the reference alone: more calls carry samples than there are slots, so a slot is taken again with its samples unfetched
+    assert sum(1 for call in want if any(len(c[5]) for c in call)) >= 4
+    td = run_unpolled(sa, x, 8000, calls, np.float32, TIME_MAJOR, lambda td: td.set_audio_capture(BOTH, TAIL, MAXB, x.size))
+    return td, [c for call in want for c in call]
+
+
+def test_calls_nobody_polls_between(sa):
+    td, flat = unpolled_audio(sa)
+    got = td.poll_audio()
+    assert all(int(r["reserved"]) == 0 and int(r["n_samples"]) == len(a) and a.dtype == np.float32 for r, a in got)
+    assert_same_chunks([[tuple(int(r[f]) for f in AUDIO_FIELDS) + (a,) for r, a in got]], [flat], "one poll behind all calls")
+    assert td.poll_audio() == []
+
+
+def test_a_view_dropped_in_parts(sa):
+    import ctypes
+    td, flat = unpolled_audio(sa)
+    assert_view_dropped_in_parts(td, td._L.same_tone_audio_peek, td._L.same_tone_audio_drop, sa.TONE_AUDIO_CHUNK_DTYPE, AUDIO_FIELDS,
+                                 ctypes.c_float, flat, assert_same_chunks)

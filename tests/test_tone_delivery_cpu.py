@@ -1,6 +1,7 @@
 """Tone-alert audio in delivery form: the host plan (sameold_amd/csrc/same_tone_delivery_plan.h) and the device core
 (same_tone_delivery_dev.h: the text the device runs) compiled with plain g++ under ASan + UBSan, driven by
-tests/helpers/tone_delivery_main.cpp the way same_tones.hip and same_tone_delivery.hip drive them, and held bit for bit
+tests/helpers/tone_delivery_main.cpp the way same_tones.hip and same_tone_delivery.hip drive them (the harvest, the
+published view and the drop are the library's own: same_tone_queue.h), and held bit for bit
 against the numpy reference (tests/helpers/tone_delivery_reference.py): every chunk's record and int16 samples in queue order,
 at 8 000 -> 8 000, 8 000 -> 4 000 (T = 32), 22 050 -> 8 000 (T = 46) and 48 000 -> 8 000 (T = 96, the limit), over three cuts of
 the same streams -- one with calls of 1, 1, 2, T - 2, T - 1 and T rows inside open captures and a ragged call that gives a

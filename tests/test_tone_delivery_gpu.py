@@ -3,7 +3,8 @@ against the numpy restatement of its contract (tests/helpers/tone_delivery_refer
 samples bit for bit, in queue order, over 130 channels (two whole groups of 64 and a partial one) x 60 blocks, both layouts, f32
 and int16, plain and ragged calls, at 8 000 -> 8 000, 8 000 -> 4 000 and 22 050 -> 8 000, and once at the tap limit
 (48 000 -> 8 000, 66 channels), on the cut that puts calls of 1, 1, 2, T - 2, T - 1 and T rows inside open captures; a group in
-which nobody captures; a pool that fills; the int16 identity; the refusals.  The streams, the patterns and the call tensors
+which nobody captures; a pool that fills; the int16 identity; the refusals; calls that nobody polls between and a view dropped
+in parts, as test_tone_audio_gpu.py has them.  The streams, the patterns and the call tensors
 are test_tone_audio_gpu.py's."""
 import os
 import sys
@@ -19,7 +20,7 @@ import tones_reference as tr  # noqa: E402
 import tone_audio_reference as ar  # noqa: E402
 import tone_delivery_reference as dr  # noqa: E402
 from test_tone_audio_gpu import (BOTH, C1, CAPTURING, CHANNEL_MAJOR, MAXB, NOISE, SILENCE, TAIL, TIME_MAJOR, TWO_TONE, TWO_TONE_OFF,  # noqa: E402
-                                 WAT_LONG, base_streams, calls_of, device_input)
+                                 WAT_LONG, assert_view_dropped_in_parts, base_streams, calls_of, device_input, run_unpolled)
 
 pytestmark = pytest.mark.gpu
 
@@ -248,3 +249,30 @@ def test_a_handle_in_float_capture_mode_is_what_it_was(sa):
         got = td.poll_audio()
         assert [(int(r["channel"]), int(r["flags"]), int(r["kind"]), int(r["sample_counter"]), int(r["tone_start"])) for r, a in got] == [c[:5] for c in w]
         assert all(np.array_equal(a.view(np.uint32), c[5].view(np.uint32)) for (r, a), c in zip(got, w))
+
+
+DELIVERY_FIELDS = ("channel", "flags", "kind", "sample_counter", "tone_start", "out_index")
+
+
+def unpolled_delivery(sa):
+    x, calls, want, _ = case(8000, 4000, "skip", True)
+    # the reference alone: more calls carry samples than there are slots, so a slot is taken again with its samples unfetched
+    assert sum(1 for call in want if any(len(c[6]) for c in call)) >= 4
+    td = run_unpolled(sa, x, 8000, calls, np.int16, CHANNEL_MAJOR, lambda td: td.set_audio_delivery(BOTH, TAIL, MAXB, x.size, 4000, 1.0))
+    return td, [c for call in want for c in call]
+
+
+def test_calls_nobody_polls_between(sa):
+    td, flat = unpolled_delivery(sa)
+    assert td.poll_audio() == []
+    got = td.poll_delivery()
+    assert all(int(r["rate"]) == 4000 and int(r["n_samples"]) == len(a) and a.dtype == np.int16 for r, a in got)
+    assert_same_chunks([[tuple(int(r[f]) for f in DELIVERY_FIELDS) + (a,) for r, a in got]], [flat], "one poll behind all calls")
+    assert td.poll_delivery() == []
+
+
+def test_a_view_dropped_in_parts(sa):
+    import ctypes
+    td, flat = unpolled_delivery(sa)
+    assert_view_dropped_in_parts(td, td._L.same_tone_delivery_peek, td._L.same_tone_delivery_drop, sa.TONE_DELIVERY_CHUNK_DTYPE,
+                                 DELIVERY_FIELDS, ctypes.c_int16, flat, assert_same_chunks)
