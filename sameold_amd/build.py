@@ -29,7 +29,7 @@ SOURCES = ["same_kernels.hip", "same_kernels_fast.hip", "same_kernels_pipe.hip",
 # operations and their order are the source's either way (-ffp-contract=off: the scheduler reorders, it does not reassociate)
 SOURCE_FLAGS = {"same_kernels_sym_hi.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 "same_kernels_pipe.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
-HEADERS = ["same_dev_common.h", "same_fast_common.h", "same_relaxed_common.h", "same_pipe_common.h", "same_profile.h", "same_device.h", "same_hipmem.h", "same_launch.h", "same_select.h", "same_tp_plan.h", "same_config.h", "same_transport.h", "same_transport_dev.h", "same_capture_dev.h", "same_resets.h", "same_harvest.h", "same_resample_dev.h", "same_resample_plan.h", "same_tones_dev.h", "same_tones_plan.h", "same_tone_audio_dev.h", "same_tone_audio_plan.h", "same_tone_audio_kernels.h", "same_tone_delivery_dev.h", "same_tone_delivery_plan.h", "same_tone_delivery_kernels.h", "same_tone_queue.h", "../../include/same_rx.h", "../../include/same_resample.h", "../../include/same_tones.h", "../../include/same_tone_audio.h", "../../include/same_tone_delivery.h",
+HEADERS = ["same_dev_common.h", "same_fast_common.h", "same_relaxed_common.h", "same_pipe_common.h", "same_piece_launch.h", "same_profile.h", "same_device.h", "same_hipmem.h", "same_launch.h", "same_select.h", "same_tp_plan.h", "same_config.h", "same_transport.h", "same_transport_dev.h", "same_capture_dev.h", "same_resets.h", "same_harvest.h", "same_resample_dev.h", "same_resample_plan.h", "same_tones_dev.h", "same_tones_plan.h", "same_tone_audio_dev.h", "same_tone_audio_plan.h", "same_tone_audio_kernels.h", "same_tone_delivery_dev.h", "same_tone_delivery_plan.h", "same_tone_delivery_kernels.h", "same_tone_queue.h", "../../include/same_rx.h", "../../include/same_resample.h", "../../include/same_tones.h", "../../include/same_tone_audio.h", "../../include/same_tone_delivery.h",
            "../../include/same_place.h", "samedec_main.cpp"]
 SAMEDEC = os.path.join(HERE, "samedec_gpu")      # the command-line decoder (host-only program, dlopens LIB)
 ARCH = "gfx950"

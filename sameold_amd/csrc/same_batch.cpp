@@ -461,7 +461,7 @@ int harvest_messages(same_batch *rx, same_batch::Slot &sl, std::chrono::steady_c
 }
 
 // The wake table re-armed in stream order (batches that ran ragged launches): the launch still in flight, if any, moves its
-// channels' instants on the device as it ends (demod_ragged_kernel), so the table goes in behind it with that launch's shifts
+// channels' instants on the device as it ends (demod_kernel's RAGGED form), so the table goes in behind it with that launch's shifts
 // added -- what the device would hold had the host's values been there before it.  The copy is queued on that launch's stream
 // and its done event moves behind the copy (later launches, harvests and the input-lifetime contract wait for that event).
 // The pinned source is the harvested slot's: the next write to it is that slot's next harvest, behind the copy.

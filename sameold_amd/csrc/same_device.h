@@ -127,7 +127,7 @@ struct State {
     uint64_t *trace_idx;   // [C][trace_cap]
 };
 
-// Time-parallel chunks (same_kernels_pipe.hip).  A launch over n_chunks * in_channels
+// Time-parallel chunks (the launchers' checks on them: same_piece_launch.h).  A launch over n_chunks * in_channels
 // state columns: column chunk * in_channels + cin demodulates input column cin from block
 // chunk * stride_blocks of the call on.  Chunk 0 starts from the channel's real state, the others from
 // a reset receiver `warm-up` samples before the range they own; every chunk but the last runs

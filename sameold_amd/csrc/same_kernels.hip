@@ -41,17 +41,41 @@ namespace same {
 // processing of a lane changes its lock, the AGC outputs after the fire offset are
 // recomputed from the saved gain ("replay"), which reproduces the sequential result
 // exactly.
+//
+// RAGGED, the ragged remainder (same_batch_process_*_ragged): the same
+// scheme over rows [0, n_rows) of which lane c consumes only its first
+// k_c = min(counts[c] - row_sub, n_rows) (0 when counts[c] <= row_sub).  Rows beyond a
+// lane's count are never loaded.  The ring positions stay wave-uniform and advance with
+// the wavefront (which runs to the largest k_c among its lanes); a lane that stopped
+// early leaves its rings frozen in LDS.  At the store, LDS slot j goes to state slot
+// (j + n_rows - k_c) mod size: the state is then canonical at the batch's new counter
+// counter0 + n_rows, where every kernel phases the rings.  The forced-EOM wake-up
+// (State::wake_sample, in batch sample coordinates) moves by the same n_rows - k_c.
+// (!RAGGED: every lane takes all n_rows; counts and row_sub are not looked at, and the launcher passes none.)
 // ---------------------------------------------------------------------------------
-template <int B, typename SampleT>
+template <int B, typename SampleT, bool RAGGED>
 __global__ __launch_bounds__(kWave) void demod_kernel(Params P, State S, Output O,
                                                       const float4 *__restrict__ taps,
                                                       const SampleT *__restrict__ x,
-                                                      uint32_t n_samples, uint64_t counter0)
+                                                      uint32_t n_rows, uint64_t counter0,
+                                                      const uint32_t *__restrict__ counts, uint32_t row_sub)
 {
     extern __shared__ float lds[];
     const uint32_t lane = threadIdx.x;
     const uint32_t C = P.n_channels;
     const uint32_t c_raw = blockIdx.x * kWave + lane;
+    uint32_t kc = n_rows, kw = n_rows;                      // this lane's samples, and the wavefront's length
+    if constexpr (RAGGED) {
+        kc = 0;
+        if (c_raw < C) {
+            const uint32_t want = counts[c_raw];
+            kc = want > row_sub ? min(want - row_sub, n_rows) : 0u;
+        }
+        // the wavefront's length: its longest lane (every lane still active here)
+        kw = kc;
+        for (int off = 32; off > 0; off >>= 1) kw = max(kw, (uint32_t)__shfl_xor((int)kw, off));
+        kw = (uint32_t)__builtin_amdgcn_readfirstlane((int)kw);
+    }
     if (c_raw >= C) return;                                 // no barriers below: tail lanes just leave
     const uint32_t c = c_raw;
     const uint32_t DL = P.dc_len;
@@ -74,144 +98,10 @@ __global__ __launch_bounds__(kWave) void demod_kernel(Params P, State S, Output 
     lane_load(L, S, c);
     GlobalCtx X{S, c, C};
 
-    for (uint32_t t0 = 0; t0 < n_samples; t0 += B) {
-        const uint32_t nb = min((uint32_t)B, n_samples - t0);
-        float xs[B];
-#pragma unroll
-        for (int k = 0; k < B; ++k)
-            xs[k] = (k < (int)nb) ? (float)x[(size_t)(t0 + k) * C + c] : 0.0f;
-
-        float ys[B];
-        int fire_k = -1;
-        float fire_rem = 0.0f, fire_gain = 0.0f;
-        const float unlocked0 = (L.flags & F_AGC_LOCKED) ? 0.0f : 1.0f;
-#pragma unroll
-        for (int k = 0; k < B; ++k) {
-            if (k < (int)nb) {
-                // DCBlocker::filter rx/dcblock.rs:45-49, MovingAverage::filter :104-108
-                const uint32_t dnext = (dpos + 1u == DL) ? 0u : dpos + 1u;
-                float aged0 = ff[dpos * kWave + lane];
-                ff[dpos * kWave + lane] = xs[k];
-                float d0 = xs[k] - aged0;
-                L.sum0 += d0;
-                float ma0 = L.sum0 * P.dc_inv_len;
-                float sig = ff[dnext * kWave + lane];       // window.front() after the push
-                float aged1 = fb[dpos * kWave + lane];
-                fb[dpos * kWave + lane] = ma0;
-                float d1 = ma0 - aged1;
-                L.sum1 += d1;
-                float ma1 = L.sum1 * P.dc_inv_len;
-                float km = P.dc_k * ma1;
-                float y = sig - km;
-                ys[k] = y;
-                dpos = dnext;
-                // Agc::input rx/agc.rs:72-77
-                float out = y * L.gain;
-                float e = 1.0f - fabsf(out);
-                float ke = unlocked0 * e;
-                float upd = ke * P.agc_bw;
-                L.gain += upd;
-                L.gain = rs_clamp(L.gain, P.agc_min, P.agc_max);
-                // demod.push_scalar receiver.rs:346
-                win[((wpos + k) & wmask) * kWave + lane] = out;
-                // sample clock receiver.rs:347-355
-                L.ted_clock += 1;
-                float rem = L.until_next_ted - (float)L.ted_clock;
-                bool fire = (fire_k < 0) && (rem <= 0.0f || fabsf(rem) < 0.5f);
-                if (fire) { fire_k = k; fire_rem = rem; fire_gain = L.gain; L.ted_clock = 0; }
-            }
-        }
-
-        if (fire_k >= 0) {
-            const uint32_t newest = (wpos + (uint32_t)fire_k) & wmask;
-            float sa_low = demod_now(P, taps, win, newest, lane);
-            const uint32_t locked_before = L.flags & F_AGC_LOCKED;
-            ted_instant(P, L, S, O, X, c, sa_low, fire_rem, counter0 + t0 + (uint32_t)fire_k + 1u);
-            if ((L.flags & F_AGC_LOCKED) != locked_before) {
-                // replay the AGC over the samples after the TED instant with the new lock
-                const float unl = (L.flags & F_AGC_LOCKED) ? 0.0f : 1.0f;
-                float g = fire_gain;
-#pragma unroll
-                for (int k = 0; k < B; ++k) {
-                    if (k > fire_k && k < (int)nb) {
-                        float out = ys[k] * g;
-                        float e = 1.0f - fabsf(out);
-                        float ke = unl * e;
-                        float upd = ke * P.agc_bw;
-                        g += upd;
-                        g = rs_clamp(g, P.agc_min, P.agc_max);
-                        win[((wpos + k) & wmask) * kWave + lane] = out;
-                    }
-                }
-                L.gain = g;
-            }
-        }
-        wpos = (wpos + nb) & wmask;
-    }
-
-    lane_store(L, S, c);
-    for (uint32_t i = 0; i < DL; ++i) {
-        S.dc_ff_ring[i * C + c] = ff[i * kWave + lane];
-        S.dc_fb_ring[i * C + c] = fb[i * kWave + lane];
-    }
-    for (uint32_t i = 0; i < P.win_ring; ++i) S.win_ring[i * C + c] = win[i * kWave + lane];
-}
-
-// ---------------------------------------------------------------------------------
-// The ragged remainder (same_batch_process_*_ragged): demod_kernel's
-// scheme over rows [0, n_rows) of which lane c consumes only its first
-// k_c = min(counts[c] - row_sub, n_rows) (0 when counts[c] <= row_sub).  Rows beyond a
-// lane's count are never loaded.  The ring positions stay wave-uniform and advance with
-// the wavefront (which runs to the largest k_c among its lanes); a lane that stopped
-// early leaves its rings frozen in LDS.  At the store, LDS slot j goes to state slot
-// (j + n_rows - k_c) mod size: the state is then canonical at the batch's new counter
-// counter0 + n_rows, where every kernel phases the rings.  The forced-EOM wake-up
-// (State::wake_sample, in batch sample coordinates) moves by the same n_rows - k_c.
-// ---------------------------------------------------------------------------------
-template <int B, typename SampleT>
-__global__ __launch_bounds__(kWave) void demod_ragged_kernel(Params P, State S, Output O,
-                                                             const float4 *__restrict__ taps,
-                                                             const SampleT *__restrict__ x,
-                                                             uint32_t n_rows, const uint32_t *__restrict__ counts,
-                                                             uint32_t row_sub, uint64_t counter0)
-{
-    extern __shared__ float lds[];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t C = P.n_channels;
-    const uint32_t c_raw = blockIdx.x * kWave + lane;
-    uint32_t kc = 0;
-    if (c_raw < C) {
-        const uint32_t want = counts[c_raw];
-        kc = want > row_sub ? min(want - row_sub, n_rows) : 0u;
-    }
-    // the wavefront's length: its longest lane (every lane still active here)
-    uint32_t kw = kc;
-    for (int off = 32; off > 0; off >>= 1) kw = max(kw, (uint32_t)__shfl_xor((int)kw, off));
-    kw = (uint32_t)__builtin_amdgcn_readfirstlane((int)kw);
-    if (c_raw >= C) return;                                 // no barriers below: tail lanes just leave
-    const uint32_t c = c_raw;
-    const uint32_t DL = P.dc_len;
-    float *ff = lds;                                        // [DL][64]
-    float *fb = lds + DL * kWave;                           // [DL][64]
-    float *win = lds + 2 * DL * kWave;                      // [win_ring][64]
-    const uint32_t wmask = P.win_ring - 1u;
-
-    uint32_t dpos = (uint32_t)(counter0 % DL);
-    uint32_t wpos = (uint32_t)(counter0 & wmask);
-
-    for (uint32_t i = 0; i < DL; ++i) {
-        ff[i * kWave + lane] = S.dc_ff_ring[i * C + c];
-        fb[i * kWave + lane] = S.dc_fb_ring[i * C + c];
-    }
-    for (uint32_t i = 0; i < P.win_ring; ++i) win[i * kWave + lane] = S.win_ring[i * C + c];
-
-    Lane L;
-    lane_load(L, S, c);
-    GlobalCtx X{S, c, C};
-
     for (uint32_t t0 = 0; t0 < kw; t0 += B) {
-        const uint32_t nb = min((uint32_t)B, kw - t0);                  // wave-uniform
-        const uint32_t lb = kc > t0 ? min((uint32_t)B, kc - t0) : 0u;   // this lane's samples of the block
+        const uint32_t nb = min((uint32_t)B, kw - t0);      // wave-uniform
+        uint32_t lb = nb;                                   // this lane's samples of the block
+        if constexpr (RAGGED) lb = kc > t0 ? min((uint32_t)B, kc - t0) : 0u;
         float xs[B];
 #pragma unroll
         for (int k = 0; k < B; ++k)
@@ -225,14 +115,14 @@ __global__ __launch_bounds__(kWave) void demod_ragged_kernel(Params P, State S, 
         for (int k = 0; k < B; ++k) {
             if (k < (int)nb) {
                 const uint32_t dnext = (dpos + 1u == DL) ? 0u : dpos + 1u;
-                if (k < (int)lb) {
+                if (!RAGGED || k < (int)lb) {
                     // DCBlocker::filter rx/dcblock.rs:45-49, MovingAverage::filter :104-108
                     float aged0 = ff[dpos * kWave + lane];
                     ff[dpos * kWave + lane] = xs[k];
                     float d0 = xs[k] - aged0;
                     L.sum0 += d0;
                     float ma0 = L.sum0 * P.dc_inv_len;
-                    float sig = ff[dnext * kWave + lane];
+                    float sig = ff[dnext * kWave + lane];       // window.front() after the push
                     float aged1 = fb[dpos * kWave + lane];
                     fb[dpos * kWave + lane] = ma0;
                     float d1 = ma0 - aged1;
@@ -248,6 +138,7 @@ __global__ __launch_bounds__(kWave) void demod_ragged_kernel(Params P, State S, 
                     float upd = ke * P.agc_bw;
                     L.gain += upd;
                     L.gain = rs_clamp(L.gain, P.agc_min, P.agc_max);
+                    // demod.push_scalar receiver.rs:346
                     win[((wpos + k) & wmask) * kWave + lane] = out;
                     // sample clock receiver.rs:347-355
                     L.ted_clock += 1;
@@ -289,22 +180,29 @@ __global__ __launch_bounds__(kWave) void demod_ragged_kernel(Params P, State S, 
     }
 
     lane_store(L, S, c);
-    // the rotated store: the lane's next slot (counter0 + k_c) becomes the batch's (counter0 + n_rows)
-    const uint32_t lag = n_rows - kc;
-    const uint32_t dr = lag % DL;
-    for (uint32_t i = 0; i < DL; ++i) {
-        const uint32_t s = (i + dr >= DL) ? i + dr - DL : i + dr;
-        S.dc_ff_ring[s * C + c] = ff[i * kWave + lane];
-        S.dc_fb_ring[s * C + c] = fb[i * kWave + lane];
-    }
-    for (uint32_t i = 0; i < P.win_ring; ++i) S.win_ring[((i + lag) & wmask) * C + c] = win[i * kWave + lane];
-    // the forced-EOM instant counts in batch samples: it moves with the channel's lag (a reported one stays reported)
-    if (lag && L.wake_sample != 0) {
-        S.wake_sample[c] = L.wake_sample + lag;
-        if (L.wake_fired == L.wake_sample) S.wake_fired[c] = L.wake_fired + lag;
+    if constexpr (RAGGED) {
+        // the rotated store: the lane's next slot (counter0 + k_c) becomes the batch's (counter0 + n_rows)
+        const uint32_t lag = n_rows - kc;
+        const uint32_t dr = lag % DL;
+        for (uint32_t i = 0; i < DL; ++i) {
+            const uint32_t s = (i + dr >= DL) ? i + dr - DL : i + dr;
+            S.dc_ff_ring[s * C + c] = ff[i * kWave + lane];
+            S.dc_fb_ring[s * C + c] = fb[i * kWave + lane];
+        }
+        for (uint32_t i = 0; i < P.win_ring; ++i) S.win_ring[((i + lag) & wmask) * C + c] = win[i * kWave + lane];
+        // the forced-EOM instant counts in batch samples: it moves with the channel's lag (a reported one stays reported)
+        if (lag && L.wake_sample != 0) {
+            S.wake_sample[c] = L.wake_sample + lag;
+            if (L.wake_fired == L.wake_sample) S.wake_fired[c] = L.wake_fired + lag;
+        }
+    } else {
+        for (uint32_t i = 0; i < DL; ++i) {
+            S.dc_ff_ring[i * C + c] = ff[i * kWave + lane];
+            S.dc_fb_ring[i * C + c] = fb[i * kWave + lane];
+        }
+        for (uint32_t i = 0; i < P.win_ring; ++i) S.win_ring[i * C + c] = win[i * kWave + lane];
     }
 }
-
 // ---------------------------------------------------------------------------------
 // layout adaptor: channel-major x[c][t] -> time-major y[t][c], 64x64 tiles through LDS
 // ---------------------------------------------------------------------------------
@@ -483,8 +381,8 @@ static hipError_t launch_demod_t(const Params &P, const State &S, const Output &
     const uint32_t grid = (P.n_channels + kWave - 1) / kWave;
     const size_t lds = (size_t)(2 * P.dc_len + P.win_ring) * kWave * sizeof(float);
 #define SAME_LAUNCH(BV)                                                                          \
-    hipLaunchKernelGGL((demod_kernel<BV, SampleT>), dim3(grid), dim3(kWave), lds, stream, P, S, \
-                       O, taps, x, n_samples, counter0)
+    hipLaunchKernelGGL((demod_kernel<BV, SampleT, false>), dim3(grid), dim3(kWave), lds, stream, P, S, \
+                       O, taps, x, n_samples, counter0, nullptr, 0u)
     switch (P.block_len) {
     case 16: SAME_LAUNCH(16); break;
     case 8: SAME_LAUNCH(8); break;
@@ -512,8 +410,8 @@ static hipError_t launch_demod_ragged_t(const Params &P, const State &S, const O
     const uint32_t grid = (P.n_channels + kWave - 1) / kWave;
     const size_t lds = (size_t)(2 * P.dc_len + P.win_ring) * kWave * sizeof(float);
 #define SAME_LAUNCH(BV)                                                                                 \
-    hipLaunchKernelGGL((demod_ragged_kernel<BV, SampleT>), dim3(grid), dim3(kWave), lds, stream, P, S, \
-                       O, taps, x, n_rows, counts, row_sub, counter0)
+    hipLaunchKernelGGL((demod_kernel<BV, SampleT, true>), dim3(grid), dim3(kWave), lds, stream, P, S, \
+                       O, taps, x, n_rows, counter0, counts, row_sub)
     switch (P.block_len) {
     case 16: SAME_LAUNCH(16); break;
     case 8: SAME_LAUNCH(8); break;

@@ -32,6 +32,7 @@
 #include "same_device.h"
 #include "same_fast_common.h"
 #include "same_launch.h"
+#include "same_piece_launch.h"
 #include "same_pipe_common.h"
 #include "same_profile.h"
 #include "same_relaxed_common.h"
@@ -1309,23 +1310,12 @@ static hipError_t launch_pipe_one(const Params &P, const State &S, const Output 
     // The two-per-CU builds (what time-parallel launches and batches beyond 16 384 channels run): one build per input
     // form (see SampleStage); everything else decides at run time
     constexpr bool FORMS = (FM && NT == 42) || (SHARE && SPLIT && LANES == 64);
-    const bool cm = K.n_chunks > 1u && K.col_row0 != nullptr;
+    const bool cm = piece_per_column(K);
     auto *kernel = !FORMS ? demod_pipe_kernel<NT, NFF, NFB, M3, SHARE, LANES, SPLIT, SampleT, FM, 2>
                           : (cm ? demod_pipe_kernel<NT, NFF, NFB, M3, SHARE, LANES, SPLIT, SampleT, FM, FORMS ? 1 : 2>
                                 : demod_pipe_kernel<NT, NFF, NFB, M3, SHARE, LANES, SPLIT, SampleT, FM, FORMS ? 0 : 2>);
-    if (lds > 64u * 1024u) {
-        // more than the default 64 KB of dynamic LDS per workgroup: opt in, once per kernel and device
-        static bool opted_in[2][64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!opted_in[cm][dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            opted_in[cm][dev] = true;
-        }
-    }
-    if (K.n_chunks > 1u && (K.in_channels % (uint32_t)LANES) != 0u) return hipErrorInvalidValue;   // a workgroup would straddle chunks
+    if (const hipError_t e = lds_opt_in(reinterpret_cast<const void *>(kernel), lds); e != hipSuccess) return e;
+    if (piece_straddles(K, (uint32_t)LANES)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kernel, dim3(P.n_channels / (uint32_t)LANES), dim3((DCW ? 5 : 4) * kWave), lds, stream, P, S, O, taps, x, n_blocks, counter0, K);
     return hipGetLastError();
 }
@@ -1434,7 +1424,7 @@ extern "C" int same_debug_filter_forms(int n_chunks, const void *d_taps, const f
     const size_t lds = ((size_t)((n_chunks * kRelaxChunk * 4 + 63) / 64 * 64) + (size_t)2 * kFormsRing * kWave) * sizeof(float);
     const float4 *t = static_cast<const float4 *>(d_taps);
     auto go = [&](auto kernel) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+        if (lds_opt_in(reinterpret_cast<const void *>(kernel), lds) != hipSuccess) return 1;
         hipLaunchKernelGGL(kernel, dim3(1), dim3(kWave), lds, nullptr, t, d_win, d_out);
         return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? 0 : 1;
     };

@@ -42,6 +42,7 @@
 #include "same_device.h"
 #include "same_fast_common.h"
 #include "same_launch.h"
+#include "same_piece_launch.h"
 #include "same_profile.h"
 #include "same_relaxed_common.h"
 
@@ -790,8 +791,8 @@ static hipError_t launch_relaxed_t(const Params &P, const State &S, const Output
                                    const SampleT *x, uint32_t n_blocks, uint64_t counter0, hipStream_t stream,
                                    const PipeChunks &K)
 {
-    if (K.n_chunks > 1u && (K.in_channels % kWave) != 0u) return hipErrorInvalidValue;   // a wavefront would straddle chunks
-    const bool cm = K.n_chunks > 1u && K.col_row0 != nullptr;
+    if (piece_straddles(K, kWave)) return hipErrorInvalidValue;
+    const bool cm = piece_per_column(K);
     if (cm && !std::is_same<SampleT, float>::value) return hipErrorInvalidValue;
     if (P.n_channels > 0x7fffffffu / 64u / sizeof(SampleT)) return hipErrorInvalidValue;   // a block of rows within a buffer resource
     const bool eq64 = P.eq_nff == 6u && P.eq_nfb == 4u, ticks = P.ticks != 0u;

@@ -53,15 +53,13 @@
 
 #include <cmath>
 #include <cstdlib>
-#include <mutex>
-#include <set>
 #include <type_traits>
-#include <utility>
 
 #include "same_dev_common.h"
 #include "same_device.h"
 #include "same_fast_common.h"
 #include "same_launch.h"
+#include "same_piece_launch.h"
 #include "same_pipe_common.h"
 #include "same_profile.h"
 #include "same_relaxed_common.h"
@@ -2050,26 +2048,12 @@ static hipError_t launch_sym_one(const Params &P, const State &S, const Output &
     constexpr uint32_t kSymHalves = (uint32_t)SymLayout<NT>::HALVES;
     constexpr size_t lds = (size_t)kSymHalves * SymLayout<NT>::lds_bytes;
     static_assert(lds <= 160u * 1024u, "one workgroup per CU");
-    const bool cm = K.n_chunks > 1u && K.col_row0 != nullptr;
+    const bool cm = piece_per_column(K);
     if (cm && (!std::is_same<SampleT, float>::value || NT != 42)) return hipErrorInvalidValue;
-    if (K.n_chunks > 1u && (K.in_channels % kWave) != 0u) return hipErrorInvalidValue;   // a workgroup would straddle chunks
+    if (piece_straddles(K, kWave)) return hipErrorInvalidValue;
     if (n_blocks == 0u) return hipSuccess;
     auto go = [&](auto kernel) -> hipError_t {
-        if (lds > 64u * 1024u) {
-            // more than the default 64 KB of dynamic LDS per workgroup: opt in, once per kernel and device.  (Keyed on the
-            // kernel's address: the time-major and the channel-major build share this lambda's instantiation.)
-            static std::mutex mu;
-            static std::set<std::pair<const void *, int>> opted_in;
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-            const std::pair<const void *, int> key(reinterpret_cast<const void *>(kernel), dev);
-            std::lock_guard<std::mutex> lock(mu);
-            if (opted_in.find(key) == opted_in.end()) {
-                const hipError_t e = hipFuncSetAttribute(key.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-                opted_in.insert(key);
-            }
-        }
+        if (const hipError_t e = lds_opt_in(reinterpret_cast<const void *>(kernel), lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, dim3((P.n_channels / kWave + kSymHalves - 1u) / kSymHalves), dim3(kSymHalves * kSymRoles * kWave), lds, stream, P, S, O, taps, x, n_blocks, counter0, K);
         return hipGetLastError();
     };

@@ -173,11 +173,20 @@ def strict_events(sa, x, rate, builder=None, link_only=False):
     return rx.poll_events_np()
 
 
-@pytest.mark.parametrize("n_ch,seconds,chunks,noise,rate", [(256, 10.0, 8, 0.0, 22050), (512, 8.0, 4, 0.05, 22050),
-                                                            (192, 12.0, 6, 0.0, 22050), (256, 6.0, 4, 0.02, 48000),
-                                                            (128, 6.0, 3, 0.0, 44100)])
-def test_time_parallel_meets_the_contract(sa, ob, arith, n_ch, seconds, chunks, noise, rate):
+def cases(rows, n_old):
+    """The first n_old rows keep the ids they had before the `sym` column (SAME_SYM) was added."""
+    return [pytest.param(*r, id="-".join(str(v) for v in (r[:-1] if i < n_old else r))) for i, r in enumerate(rows)]
+
+
+# sym "0": SAME_SYM=0 puts the pipeline's FASTMATH build in the symbol-paced kernel's place (the smallest shape that has two
+# workgroups and a first, a middle and a last piece)
+@pytest.mark.parametrize("n_ch,seconds,chunks,noise,rate,sym", cases([(256, 10.0, 8, 0.0, 22050, None), (512, 8.0, 4, 0.05, 22050, None),
+                                                                      (192, 12.0, 6, 0.0, 22050, None), (256, 6.0, 4, 0.02, 48000, None),
+                                                                      (128, 6.0, 3, 0.0, 44100, None), (128, 6.0, 3, 0.0, 22050, "0")], 5))
+def test_time_parallel_meets_the_contract(sa, ob, arith, monkeypatch, n_ch, seconds, chunks, noise, rate, sym):
     from helpers.oracle_compare import assert_every_channel_matches_oracle
+    if sym is not None:
+        monkeypatch.setenv("SAME_SYM", sym)
     n = int(rate * seconds)
     x = sa.synth_afsk(n_ch, n, rate, seed=1000 + n_ch, noise_sigma=noise)
     ref = strict_events(sa, x, rate)
@@ -188,7 +197,7 @@ def test_time_parallel_meets_the_contract(sa, ob, arith, n_ch, seconds, chunks, 
     rx.sync()
     assert rx.time_parallel_chunks() == chunks
     # relaxed arithmetic inside the chunks at all three rates the pipeline is built for (whole 64-channel groups)
-    assert rx.kernel_name() == ("demod_pipe_kernel" if arith == "strict" else "demod_sym_kernel")
+    assert rx.kernel_name() == ("demod_pipe_kernel" if arith == "strict" else "demod_pipe_kernel<fastmath>" if sym == "0" else "demod_sym_kernel")
     got = rx.poll_events_np()
     assert len(got[got["kind"] == 3]) >= 2 * n_ch
     assert_contract(sa, got, ref, rate, n_ch, lambda c: sa.synth_payload(1000 + n_ch, c), exact_bursts=(noise == 0.0),
@@ -418,13 +427,16 @@ def test_flush_and_reset_in_time_parallel_mode(sa):
         rx.reset()
 
 
-@pytest.mark.parametrize("n_ch,seconds,chunks,noise", [(256, 10.0, 8, 0.0), (128, 12.0, 5, 0.0), (192, 9.0, 8, 0.05),
-                                                        (4096, 6.0, 12, 0.0)])      # (49 152 columns: pieces sorted into workgroups)
-def test_per_channel_boundaries_on_channel_major_input(sa, ob, arith, monkeypatch, n_ch, seconds, chunks, noise):
+@pytest.mark.parametrize("n_ch,seconds,chunks,noise,sym", cases([(256, 10.0, 8, 0.0, None), (128, 12.0, 5, 0.0, None), (192, 9.0, 8, 0.05, None),
+                                                                 (4096, 6.0, 12, 0.0, None),      # (49 152 columns: pieces sorted into workgroups)
+                                                                 (128, 8.0, 4, 0.0, "0")], 4))    # (SAME_SYM=0: the pipeline's FASTMATH build)
+def test_per_channel_boundaries_on_channel_major_input(sa, ob, arith, monkeypatch, n_ch, seconds, chunks, noise, sym):
     """A channel-major f32 input of whole blocks is read where it lies: an energy scout and a planner on the device
     put every chunk boundary of every channel at an idle instant (no run-on), each state column streams its own
     contiguous samples.  Same contract as the uniform cut."""
     monkeypatch.setenv("SAME_PIPE_LANES", "64")      # (small test batches would otherwise get 16-channel workgroups)
+    if sym is not None:
+        monkeypatch.setenv("SAME_SYM", sym)
     rate = 22050
     n = int(rate * seconds)
     n -= n % 1260                    # whole blocks of every kernel that may take the chunks (20, 36 and 42 samples)
@@ -438,6 +450,8 @@ def test_per_channel_boundaries_on_channel_major_input(sa, ob, arith, monkeypatc
     # (the planner may settle for fewer chunks than asked for when they would own too little)
     assert chunks - 1 <= rx.time_parallel_chunks() <= chunks and rx.time_parallel_per_channel()
     assert n_ch * rx.time_parallel_chunks() > 32768 or n_ch < 4096      # the big case exercises the sorted order
+    if sym == "0":
+        assert rx.kernel_name() == ("demod_pipe_kernel" if arith == "strict" else "demod_pipe_kernel<fastmath>")
     got = rx.poll_events_np()
     assert_contract(sa, got, ref, rate, n_ch, lambda c: sa.synth_payload(3000 + n_ch, c), exact_bursts=(noise == 0.0), t_end=n,
                     garbled_per_mille=(1 if noise > 0.0 and arith == "fastmath" else 0))
